@@ -23,8 +23,8 @@ collective; value = evals of all ranks / max wall time. Two ways to start it:
 Every rank asserts world size == --gpus and that its device exists; on a 1-GPU box
 `--gpus 2` fails with a message instead of reporting n_gpus: 1.
 
-With --gpus > 1 rank 0 also measures BASELINE configs[3] (N=65536) spread over all ranks
-(extra.dist) and checks its logpdf against the single-GPU evaluation of the same input in
+With --full and --gpus > 1 rank 0 also measures BASELINE configs[3] (N=65536) spread over
+all ranks (extra.dist) and checks its logpdf against the single-GPU evaluation of the same input in
 the same run (extra.dist.parity_vs_single, bar 1e-9 relative); a failed or non-matching
 dist line makes the process exit non-zero (4) after the JSON line is printed. The leg runs
 under its own deadline (--dist-deadline, 240 s, well inside the driver's limit and the
@@ -32,6 +32,20 @@ process group's 600 s collective timeout): a leg that hangs (a collective that n
 completes) becomes an error in the line instead of a job killed with no line at all;
 rank 0 prints the replicas line with dist_ok false and the process ends with status 4
 without waiting for the hung collective (bounded_leg).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure
+needs: set up, warm up, time the N steps, write the outputs if --dump-outputs is given and
+print the line. Everything else the default mode measures or checks runs only with --full:
+the CPU baseline, the roofline and per-kernel passes, the standalone Gram launch, the extra
+sizes and configurations (two chains, N=4096, N=65536, select) and, with --gpus > 1, the
+configs[3] leg and its parity check. --skip-cpu, --no-extra, --no-profile and --no-dist
+still take single legs out of a --full run. The other modes (--mode grad, posterior, ...)
+are chosen explicitly and run as before.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path returned in its last
+step as DIR/<name>.npy (float64): what a caller of that entry receives. The inputs are
+seeded, so the same arguments give the same inputs in every run, and two builds can be
+compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -144,6 +158,26 @@ def load_traffic(name=TRAFFIC_FILE):
         return d.get("bytes_per_launch"), os.path.relpath(path, HERE)
     except (OSError, ValueError):
         return None, None
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of one run together
+DUMP_HEADER_BYTES = 1024       # allowance for each file's .npy header
+
+
+def dump_outputs(dirname, outputs: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: write the last timed step's results as DIR/<name>.npy (float64; with
+    several ranks every rank writes <name>_rank<r>.npy). An output too large for its share
+    of DUMP_MAX_BYTES is written as a fixed seeded sample of its elements."""
+    if not dirname:
+        return
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.atleast_1d(np.asarray(a, dtype=np.float64)) for k, a in outputs.items() if a is not None}
+    cap = max(1, (DUMP_MAX_BYTES // (max(1, len(arrays)) * world) - DUMP_HEADER_BYTES) // 8)  # elements per file
+    for name, a in arrays.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), np.ascontiguousarray(a))
 
 
 DIST_PARITY_BAR = 1e-9  # relative, north_star's fp64 bar
@@ -305,6 +339,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", type=int, default=N_DEFAULT)
+    ap.add_argument("--full", action="store_true",
+                    help="default mode: also run everything beside the headline figure (CPU baseline, roofline and "
+                         "per-kernel passes, standalone Gram, two chains, N=4096, N=65536, select; with --gpus > 1 "
+                         "the configs[3] leg and its parity check). Off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--skip-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the extra size legs (N=4096, N=65536, select, two chains): profiling runs")
@@ -334,6 +374,8 @@ def main():
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv, need_gpus=args.mode != "launcher-check")
     if args.mode == "launcher-check":
@@ -378,11 +420,15 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, {"logpdf": lp}, rank, world)
+
+    # Everything below the timed region except the line itself runs only with --full.
+    profile = args.full and not args.no_profile
 
     # Roofline pass: the same steps with hipEvents recorded on s_main (the launching
     # stream) around every bulk tile_syrk launch (gaplac_set_profiling mode 2).
     st_ev = None
-    if not args.no_profile:
+    if profile:
         ctx.reset_stats()
         ctx.set_profiling(2)
         for i in range(max(1, min(args.steps, 5))):
@@ -393,7 +439,7 @@ def main():
     # Per-kernel breakdown (extra): per-launch device timestamps wired into every kernel
     # (first workgroup start / last wave end on the 100 MHz s_memrealtime clock).
     st = None
-    if not args.no_profile and args.profile_steps > 0:
+    if profile and args.profile_steps > 0:
         ctx.reset_stats()
         ctx.set_profiling(True)
         for i in range(args.profile_steps):
@@ -406,10 +452,10 @@ def main():
     # in-situ rate is a schedule figure; the kernel's roofline is this standalone launch of
     # the same Gram (configs[2] terms, all lower tiles, plain grid, best of 5, hipEvents).
     gram_alone = None
-    if not args.no_profile and rank == 0:
+    if profile and rank == 0:
         gram_alone = ctx.gram_time(X, terms_for(LENGTHSCALES[0]), CF.NOISE_VAR, v, reps=5)
 
-    full_run = not args.no_profile and not args.no_extra  # profiled runs keep to the timed schedule
+    full_run = profile and not args.no_extra  # profiled runs keep to the timed schedule
     # Throughput with two chains per GPU (extra, not the headline): independent evaluations
     # in flight on two lanes (gaplac_logpdf_batch), filling the latency-bound tail of one
     # evaluation's panel chain with the other's bulk updates.
@@ -437,7 +483,7 @@ def main():
     # ranks, panel broadcasts over RCCL): an extra line beside the replicas headline.
     dist_line = None
     dist_expired = False
-    if world > 1 and not args.no_dist:
+    if world > 1 and args.full and not args.no_dist:
         ctx.close()  # free the N=16384 workspace before the 65536 one
         single_lp = n65536["last_logpdf"] if n65536 else None
         dist_line, dist_expired = bounded_leg(
@@ -531,7 +577,7 @@ def main():
             extra["syrk_avg_launch_ms_stamps"] = st["syrk_ms"] / st["syrk_launches"]
 
     cpu = None
-    if world == 1 and not args.skip_cpu:
+    if world == 1 and args.full and not args.skip_cpu:
         cpu = cpu_baseline(N)
 
     out = {
@@ -800,6 +846,7 @@ def main_grad(args):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ctx.set_profiling(0)
+    dump_outputs(args.dump_outputs, {"logpdf": res[0], "dv": res[1], "dparam": res[2], "dnoise": res[3]}, rank, world)
     st_ev = ctx.stats()
     st = None
     if not args.no_profile and args.profile_steps > 0:
@@ -895,12 +942,14 @@ def main_post(args):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    res = None
     for i in range(args.steps):
-        step(i)
+        res = step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, {"mean": res[0], "var": res[1]} if post else {"draw": res}, rank, world)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -978,6 +1027,7 @@ def main_select(args):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, {"logpdf": res}, rank, world)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1038,6 +1088,7 @@ def main_dist(args):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    dump_outputs(args.dump_outputs, {"logpdf": lp}, rank, world)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
