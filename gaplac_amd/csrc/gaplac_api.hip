@@ -12,6 +12,7 @@
 #include <cstddef>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -57,7 +58,6 @@ struct gaplac_ctx {
     // 2 = hipEvents recorded on s_main around every bulk tile_syrk launch (eager launches),
     //     read back by gaplac_get_stats
     int prof_mode = 0;
-    bool profiling = false;  // prof_mode == 1
     std::vector<hipEvent_t> evpool;
     struct EvPair {
         size_t i0;
@@ -208,6 +208,61 @@ int set_err(gaplac_ctx* ctx, int code, const char* fmt, ...) {
     } while (0)
 
 int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// What a context owns, written once: gaplac_ctx_create, gaplac_ctx_destroy and
+// gaplac_ctx_release walk these lists (evpool's events and the lanes are the only other
+// resources). The struct itself stays plain: the dry runs keep one on the stack.
+std::array<hipEvent_t*, 20> ctx_events(gaplac_ctx* c) {
+    return {&c->ev_P[0],       &c->ev_P[1],       &c->ev_R[0],       &c->ev_R[1],
+            &c->ev_xc[0],      &c->ev_xc[1],      &c->ev_xr[0],      &c->ev_xr[1],
+            &c->ev_split[0],   &c->ev_split[1],   &c->ev_rest[0],    &c->ev_rest[1],
+            &c->ev_gram,       &c->ev_gram2,      &c->ev_xinit,      &c->ev_xdone,
+            &c->bw[0].ev_gram, &c->bw[0].ev_done, &c->bw[1].ev_gram, &c->bw[1].ev_done};
+}
+
+struct Buf {
+    void** p;
+    size_t* cap;   // the capacity kept beside a buffer that gaplac_ctx_release drops (else nullptr)
+    size_t fixed;  // > 0: this many bytes from gaplac_ctx_create on; 0: grown on demand
+    bool pinned;   // host memory (hipHostMalloc)
+};
+template <typename T>
+Buf buf(T** p, size_t fixed = 0, bool pinned = false, size_t* cap = nullptr) {
+    return {reinterpret_cast<void**>(p), cap, fixed, pinned};
+}
+template <typename T>
+Buf large(T** p, size_t* cap) { return buf(p, 0, false, cap); }
+
+std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
+    constexpr size_t gout_bytes = sizeof(double) * (GAPLAC_MAX_TERMS + 1);
+    std::vector<Buf> b{large(&c->A, &c->A_elems), large(&c->Dinv, &c->Dinv_elems), buf(&c->tiles), buf(&c->dX),
+                       buf(&c->dv), buf(&c->dres, sizeof(EvalResult)), buf(&c->hres, sizeof(EvalResult), true),
+                       buf(&c->dtp, sizeof(TermPack)), buf(&c->htp, sizeof(TermPack), true), buf(&c->tctl),
+                       buf(&c->ttasks), buf(&c->ttrace), buf(&c->dkt), buf(&c->hkt, 0, true), buf(&c->dXs),
+                       buf(&c->pmean), buf(&c->pvar), buf(&c->galpha), buf(&c->gdv), buf(&c->gz), buf(&c->gpart),
+                       buf(&c->gout, gout_bytes), buf(&c->hgout, gout_bytes, true), buf(&c->dgp, sizeof(GradTermPack)),
+                       buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist)};
+    for (auto& w : c->bw)
+        b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
+                           buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
+    return b;
+}
+
+void free_buf(const Buf& b) {
+    if (*b.p) (void)(b.pinned ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr;
+    if (b.cap) *b.cap = 0;
+}
+
+// Wait for everything the context has enqueued (every stream it holds); the first error.
+hipError_t sync_streams(gaplac_ctx* c) {
+    hipError_t first = hipSuccess;
+    for (hipStream_t s : {c->s_main, c->s_panel, c->s_extra, c->s_xrest}) {
+        const hipError_t e = s ? hipStreamSynchronize(s) : hipSuccess;
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
 
 }  // namespace
 
@@ -558,6 +613,11 @@ static void serial_tail(gaplac_ctx* ctx, hipStream_t sm, int64_t N, int64_t lda,
     }
 }
 
+// Super-panels per deferred bulk update (pair_depth, or by size: see gaplac_ctx::pair_depth)
+static int deferral_depth(const gaplac_ctx* ctx, int nt) {
+    return ctx->pair_depth > 0 ? ctx->pair_depth : nt >= 256 ? 4 : 2;
+}
+
 // Paired bulk updates (GAPLAC_PAIR_M): does step p defer its bulk update
 // (only the next-needed bands get SP p; the columns after them get SPs p and p+1 together
 // at step p+1)? pend: the super-panel still pending (-1: none).
@@ -565,10 +625,9 @@ static bool pair_defer(const gaplac_ctx* ctx, const std::vector<int>& spc, int n
     const int nsp = (int)spc.size() - 1;
     const int jb = p + 2 <= nsp ? spc[(size_t)p + 2] : spc[(size_t)nsp];
     const int je = p + 3 <= nsp ? spc[(size_t)p + 3] : spc[(size_t)nsp];
-    const int depth = ctx->pair_depth > 0 ? ctx->pair_depth : nt >= 256 ? 4 : 2;
-    return ctx->pair_m > 0 && (pend < 0 || p - pend + 1 < depth) && !ctx->serial && !ctx->xr_mode && je > jb &&
-           p + 1 + ctx->pair_ext < nsp &&
-           p + 3 + ctx->pair_ext <= nsp && nt - spc[(size_t)p + 3 + ctx->pair_ext] >= ctx->pair_m;
+    return ctx->pair_m > 0 && (pend < 0 || p - pend + 1 < deferral_depth(ctx, nt)) && !ctx->serial &&
+           !ctx->xr_mode && je > jb && p + 1 + ctx->pair_ext < nsp && p + 3 + ctx->pair_ext <= nsp &&
+           nt - spc[(size_t)p + 3 + ctx->pair_ext] >= ctx->pair_m;
 }
 
 // Latency-shaped (quadrant) columns of a single evaluation's tail: with the simulated
@@ -612,13 +671,64 @@ constexpr int SPLIT_REST_MIN = 16;
 #define GAPLAC_SPLIT_DEPTH 2  // deferral depths the split applies to (the head is depth x W columns)
 #endif
 static bool split_wanted(const gaplac_ctx* ctx, int nt) {
-    const int depth = ctx->pair_depth > 0 ? ctx->pair_depth : nt >= 256 ? 4 : 2;
     const std::vector<int> spc = superpanel_starts(ctx, nt);  // (a short super-panel phase: not worth it)
-    return GAPLAC_SPLIT && ctx->xr_mode == 0 && !ctx->serial && depth <= GAPLAC_SPLIT_DEPTH &&
+    return GAPLAC_SPLIT && ctx->xr_mode == 0 && !ctx->serial && deferral_depth(ctx, nt) <= GAPLAC_SPLIT_DEPTH &&
            !whole_in_tail(ctx, nt) && spc.back() >= GAPLAC_SPLIT_MINCOLS;
 }
 static bool split_bulk(const gaplac_ctx* ctx, int nt) {
     return split_wanted(ctx, nt) && (ctx->s_xrest != nullptr || ctx->dry);
+}
+
+// Profiling mode 2: `launch` between two hipEvents on its stream st when `timed` (a pair of
+// evpool, grown on first use; gaplac_get_stats reads the pairs back as pr describes them).
+template <typename Launch>
+int timed_launch(gaplac_ctx* ctx, bool timed, hipStream_t st, gaplac_ctx::EvPair pr, Launch&& launch) {
+    if (timed) {
+        pr.i0 = 2 * ctx->evpairs.size();
+        while (ctx->evpool.size() < pr.i0 + 2) {
+            hipEvent_t e;
+            HIPQ(ctx, hipEventCreate(&e));
+            ctx->evpool.push_back(e);
+        }
+        HIPQ(ctx, hipEventRecord(ctx->evpool[pr.i0], st));
+    }
+    launch();
+    if (timed) {
+        HIPQ(ctx, hipEventRecord(ctx->evpool[pr.i0 + 1], st));
+        ctx->evpairs.push_back(pr);
+    }
+    return 0;
+}
+
+// The band list's launch: the W tile columns from b0 of the trailing matrix (rows from their
+// diagonal down, nt - b0 tile rows) get the panel pn, K = kdep; whole: as 128x128 tiles only.
+BulkArgs band_args(const gaplac_ctx* ctx, int64_t lda, int nt, int b0, const Panel& pn, int kdep, bool whole) {
+    const int W = ctx->spw, mbd = nt - b0;
+    BulkArgs bb{ctx->A, lda, pn, ctx->tiles + ctx->band_off[(size_t)mbd], W * mbd - W * (W - 1) / 2, kdep, b0, b0,
+                ColMap{1, 0, W}};
+    bb.max_r = mbd - 1;
+    bb.max_c = W - 1;
+    bb.whole = whole ? 1 : 0;
+    return bb;
+}
+
+// ... launched on st; in profiling mode 2 whole-tile bands (heads, lookaheads, large bands:
+// kind 5) are event-timed, for the bulk phase's union of launch intervals
+int band_launch(gaplac_ctx* ctx, hipStream_t st, int64_t lda, int nt, int b0, const Panel& pn, int kdep, bool whole) {
+    const BulkArgs bb = band_args(ctx, lda, nt, b0, pn, kdep, whole);
+    return timed_launch(ctx, ctx->prof_mode == 2 && whole && !ctx->xr_mode, st,
+                        {0, band_flops(nt - b0, ctx->spw, kdep), 0.0, 5},
+                        [&] { launch_bulk(st, bb, slot(ctx, 5, 0)); });
+}
+
+// s_main waits for what the extra rows' streams hold (gradient / posterior, not serial)
+int join_extra_streams(gaplac_ctx* ctx, hipStream_t sm) {
+    if (!ctx->xr_mode || ctx->serial) return 0;
+    for (hipStream_t sx : {ctx->s_extra, ctx->s_xrest}) {
+        HIPQ(ctx, hipEventRecord(ctx->ev_xdone, sx));
+        HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
+    }
+    return 0;
 }
 
 int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
@@ -647,47 +757,19 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
         if ((frc = factor_superpanel(ctx, sp, N, lda, nt, spc[0], spc[1]))) return frc;
         HIPQ(ctx, hipEventRecord(ctx->ev_P[0], sp));
     }
-    // profiling mode 2: hipEvents around a band-type bulk launch (whole-tile bands, heads and
-    // lookaheads: kind 5) on its stream, for the bulk phase's union of launch intervals
-    auto band_launch = [&](hipStream_t st, const BulkArgs& bb, int mbd) {
-        const bool ev = ctx->prof_mode == 2 && bb.whole && !ctx->xr_mode;
-        size_t e0 = 0;
-        if (ev) {
-            e0 = 2 * ctx->evpairs.size();
-            while (ctx->evpool.size() < e0 + 2) {
-                hipEvent_t e;
-                HIPQ(ctx, hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0], st));
-        }
-        launch_bulk(st, bb, slot(ctx, 5, 0));
-        if (ev) {
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0 + 1], st));
-            ctx->evpairs.push_back({e0, band_flops(mbd, W, bb.kdepth), 0.0, 5});
-        }
-        return 0;
-    };
     // bulk trailing update of the triangle of tile columns >= j0 with the panel pn (K = kd)
     auto bulk_tri = [&](int j0, const Panel& pn, int kdep) -> int {
         if (j0 >= nt) return 0;
-        wait_rest(sm, nt);
+        if ((frc = wait_rest(sm, nt))) return frc;
         int jr = j0;  // first tile column of the triangle launch (after the head)
         hipStream_t st = sm;
-        const int hw = (ctx->pair_depth > 0 ? ctx->pair_depth : nt >= 256 ? 4 : 2) * W;  // head width
+        const int hw = deferral_depth(ctx, nt) * W;  // head width
         if (split && nt - j0 >= hw + SPLIT_REST_MIN && ctx->band_off.size() > (size_t)(nt - j0)) {
             // what s_main holds so far (this step's panel wait, earlier updates) before the rest
             HIPQ(ctx, hipEventRecord(ctx->ev_split[nsplit & 1], sm));
             // head: tile columns [j0, j0 + hw) as band launches (whole tiles) on s_main
-            for (int b0 = j0; b0 < j0 + hw; b0 += W) {
-                const int mbd = nt - b0;
-                BulkArgs bb{ctx->A, lda, pn, ctx->tiles + ctx->band_off[(size_t)mbd], W * mbd - W * (W - 1) / 2, kdep,
-                            b0, b0, ColMap{1, 0, W}};
-                bb.max_r = mbd - 1;
-                bb.max_c = W - 1;
-                bb.whole = 1;
-                band_launch(sm, bb, mbd);
-            }
+            for (int b0 = j0; b0 < j0 + hw; b0 += W)
+                if ((frc = band_launch(ctx, sm, lda, nt, b0, pn, kdep, true))) return frc;
             jr = j0 + hw;
             st = sr;
             HIPQ(ctx, hipStreamWaitEvent(sr, ctx->ev_split[nsplit & 1], 0));
@@ -698,22 +780,9 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
         const bool small = syrk_is_small(ba.ntiles);
         const double fl = syrk_flops(m) * (kdep / NB), by = syrk_bytes(m, kdep);
         KTime* kt = small ? slot(ctx, 6, 0) : slot(ctx, 0, fl, by);
-        const bool ev = ctx->prof_mode == 2 && !small;
-        size_t e0 = 0;
-        if (ev) {
-            e0 = 2 * ctx->evpairs.size();
-            while (ctx->evpool.size() < e0 + 2) {
-                hipEvent_t e;
-                HIPQ(ctx, hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0], st));
-        }
-        launch_bulk(st, ba, kt);
-        if (ev) {
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0 + 1], st));
-            ctx->evpairs.push_back({e0, fl, by, 0});
-        }
+        if ((frc = timed_launch(ctx, ctx->prof_mode == 2 && !small, st, {0, fl, by, 0},
+                                [&] { launch_bulk(st, ba, kt); })))
+            return frc;
         if (st == sr) {
             HIPQ(ctx, hipEventRecord(ctx->ev_rest[nsplit & 1], sr));
             ++nsplit;
@@ -732,23 +801,18 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
             else
                 HIPQ(ctx, hipStreamWaitEvent(sp, ctx->ev_gram2, 0));  // rest of the Gram built
             const int c2 = spc[(size_t)p + 2];
-            wait_rest(sp, c2);  // (SP p+1's columns in a split update's rest still in flight)
+            // (SP p+1's columns in a split update's rest still in flight)
+            if ((frc = wait_rest(sp, c2))) return frc;
             const int mla = nt - c1;
+            const Panel pn{ctx->A + (int64_t)c0 * NB * lda, lda, 0};
             if (GAPLAC_CHAIN_SKIP >= 2 && !ctx->dry) {
             } else if (ctx->la_tiles_m > 0 && mla >= ctx->la_tiles_m && c2 - c1 == W && ctx->band_off.size() > (size_t)mla &&
                        !ctx->xr_mode) {
                 // the lookahead as whole 128x128 tiles (the band list of SP p+1's columns):
                 // less CU time than the quadrant kernel while the trailing matrix is large
-                BulkArgs ba{ctx->A, lda, Panel{ctx->A + (int64_t)c0 * NB * lda, lda, 0},
-                            ctx->tiles + ctx->band_off[(size_t)mla], W * mla - W * (W - 1) / 2, kd, c1, c1,
-                            ColMap{1, 0, W}};
-                ba.max_r = mla - 1;
-                ba.max_c = W - 1;
-                ba.whole = 1;
-                band_launch(sp, ba, mla);
+                if ((frc = band_launch(ctx, sp, lda, nt, c1, pn, kd, true))) return frc;
             } else {
-                launch_col_update(sp, ctx->A, lda, Panel{ctx->A + (int64_t)c0 * NB * lda, lda, 0}, nt, c1, c1,
-                                  c2 - c1, kd, slot(ctx, 5, 0));
+                launch_col_update(sp, ctx->A, lda, pn, nt, c1, c1, c2 - c1, kd, slot(ctx, 5, 0));
             }
             if ((frc = factor_superpanel(ctx, sp, N, lda, nt, c1, c2))) return frc;
             HIPQ(ctx, hipEventRecord(ctx->ev_P[(p + 1) & 1], sp));
@@ -763,22 +827,16 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
         const int je = p + 3 <= nsp ? spc[(size_t)p + 3] : spc[(size_t)nsp];
         const bool defer = pair_defer(ctx, spc, nt, p, pend);
         // a band [b0, b1) with the panel columns pc .. c1-1
-        auto band = [&](int b0, int b1, int pc) {
-            if (b1 <= b0) return;
-            wait_rest(sm, b1);
+        auto band = [&](int b0, int b1, int pc) -> int {
+            if (b1 <= b0) return 0;
+            if (int rc = wait_rest(sm, b1)) return rc;
             const Panel pn{ctx->A + (int64_t)pc * NB * lda, lda, 0};
             const int kb = (c1 - pc) * NB, mbd = nt - b0;
-            if (b1 - b0 == W && ctx->band_off.size() > (size_t)mbd) {
-                // through the tile kernel (a list of the band's tiles; quadrants if small)
-                BulkArgs ba{ctx->A, lda, pn, ctx->tiles + ctx->band_off[(size_t)mbd], W * mbd - W * (W - 1) / 2, kb,
-                            b0, b0, ColMap{1, 0, W}};
-                ba.max_r = mbd - 1;
-                ba.max_c = W - 1;
-                ba.whole = mbd >= ctx->band_tiles_m ? 1 : 0;
-                band_launch(sm, ba, mbd);
-            } else {
-                launch_col_update(sm, ctx->A, lda, pn, nt, b0, b0, b1 - b0, kb, slot(ctx, 5, 0));
-            }
+            // through the tile kernel (a list of the band's tiles; quadrants if small)
+            if (b1 - b0 == W && ctx->band_off.size() > (size_t)mbd)
+                return band_launch(ctx, sm, lda, nt, b0, pn, kb, mbd >= ctx->band_tiles_m);
+            launch_col_update(sm, ctx->A, lda, pn, nt, b0, b0, b1 - b0, kb, slot(ctx, 5, 0));
+            return 0;
         };
         // first panel column a band starting at tile column b0 still lacks: columns >= dcol
         // lack every super-panel from pend on, the others only this step's
@@ -786,24 +844,21 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
         if (defer && pend >= 0) {
             // a deeper deferral (GAPLAC_PAIR_DEPTH > 2): the next-needed band gets this
             // step's panel, the band after it every panel from pend on
-            band(jb, je, first_panel(jb));
+            if ((frc = band(jb, je, first_panel(jb)))) return frc;
             HIPQ(ctx, hipEventRecord(ctx->ev_R[p & 1], sm));
             const int e1 = ctx->pair_ext > 0 ? spc[(size_t)p + 4] : je;
-            if (je < e1) band(je, e1, first_panel(je));
+            if ((frc = band(je, e1, first_panel(je)))) return frc;
             dcol = std::max(dcol, e1);
         } else if (defer) {
-            band(jb, je, c0);
+            if ((frc = band(jb, je, c0))) return frc;
             HIPQ(ctx, hipEventRecord(ctx->ev_R[p & 1], sm));
-            dcol = je;
-            if (ctx->pair_ext > 0) {
-                dcol = spc[(size_t)p + 4];
-                band(je, dcol, c0);
-            }
+            dcol = ctx->pair_ext > 0 ? spc[(size_t)p + 4] : je;
+            if ((frc = band(je, dcol, c0))) return frc;
             pend = p;
         } else if (pend >= 0) {
-            band(jb, je, je <= dcol ? c0 : spc[(size_t)pend]);
+            if ((frc = band(jb, je, je <= dcol ? c0 : spc[(size_t)pend]))) return frc;
             HIPQ(ctx, hipEventRecord(ctx->ev_R[p & 1], sm));
-            if (je < dcol) band(je, dcol, c0);  // (not produced by the schedule above)
+            if ((frc = band(je, dcol, c0))) return frc;  // (not produced by the schedule above)
             const Panel pnl{ctx->A + (int64_t)spc[(size_t)pend] * NB * lda, lda, 0};
             if ((frc = bulk_tri(std::max(je, dcol), pnl, (c1 - spc[(size_t)pend]) * NB))) return frc;
             pend = -1;
@@ -839,20 +894,15 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
             }
         }
     }
-    wait_rest(sm, nt);  // every split update's rest before the tail
+    if ((frc = wait_rest(sm, nt))) return frc;  // every split update's rest before the tail
     if (spc[(size_t)nsp] < nt) {
         const int ts = spc[(size_t)nsp], T = nt - ts;
         // the posterior's cross-covariance rows: factored along inside the tail
         const int X = ctx->xr_mode == 2 ? ctx->xr_tiles : 0;
         if (ctx->tailk && T + X <= TAIL_TMAX && (ctx->xr_mode == 0 || X > 0)) {
             // the tail as one persistent dataflow launch
-            if (ctx->xr_mode && !ctx->serial) {
-                // the extra rows' super-panel updates of the tail's columns land first
-                HIPQ(ctx, hipEventRecord(ctx->ev_xdone, ctx->s_extra));
-                HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-                HIPQ(ctx, hipEventRecord(ctx->ev_xdone, ctx->s_xrest));
-                HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-            }
+            // the extra rows' super-panel updates of the tail's columns land first
+            if ((frc = join_extra_streams(ctx, sm))) return frc;
             const bool gram = ts == 0 && gram_in_tail(ctx, nt, lda);
             if (ctx->dry) {  // gaplac_plan_check: the task list's dependency order
                 std::vector<uint32_t> host;
@@ -900,42 +950,46 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
             serial_tail(ctx, sm, N, lda, nt, ts);
         }
     }
-    if (ctx->xr_mode && !ctx->serial) {
-        HIPQ(ctx, hipEventRecord(ctx->ev_xdone, ctx->s_extra));
-        HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-        HIPQ(ctx, hipEventRecord(ctx->ev_xdone, ctx->s_xrest));
-        HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-    }
+    if ((frc = join_extra_streams(ctx, sm))) return frc;
     launch_reduce(sm, ctx->A, lda, N, (int64_t)nt * NB, ColMap{1, 0, 1}, ctx->dres);
     HIPQ(ctx, hipGetLastError());
     return 0;
 }
 
+// Where the packed lists of ctx->tiles lie for nt tile columns (set in ctx; returns their
+// total length): tile_off[m] the m x m triangle's list, m = 1..nt, then band_off[m] the band
+// list of an m-row trailing matrix (its first spw tile columns, rows r >= c, rows outer).
+size_t set_tile_layout(gaplac_ctx* ctx, int nt) {
+    size_t k = 0;
+    ctx->tile_off.assign((size_t)nt + 1, 0);
+    for (int m = 1; m <= nt; ++m) {
+        ctx->tile_off[(size_t)m] = k;
+        k += (size_t)m * (m + 1) / 2;
+    }
+    ctx->band_off.assign((size_t)nt + 1, k);
+    for (int m = 1; m <= nt; ++m) {
+        const size_t w = (size_t)std::min(ctx->spw, m);
+        ctx->band_off[(size_t)m] = k;
+        k += w * m - w * (w - 1) / 2;
+    }
+    return k;
+}
+
 // Upload the super-tile ordered lists for every triangle size m = 1..nt (once per nt).
 int ensure_tile_lists(gaplac_ctx* ctx, int nt) {
     if (ctx->tiles_nt >= nt) return 0;
-    std::vector<size_t> off((size_t)nt + 1, 0);
-    for (int m = 1; m <= nt; ++m) off[(size_t)m] = off[(size_t)m - 1] + (size_t)(m - 1) * m / 2;
-    const size_t tri_total = off[(size_t)nt] + (size_t)nt * (nt + 1) / 2;
-    const int w = ctx->spw;
-    size_t total = tri_total;
-    for (int m = 1; m <= nt; ++m) total += (size_t)std::min(w, m) * m - (size_t)std::min(w, m) * (std::min(w, m) - 1) / 2;
+    ctx->tiles_nt = 0;  // (until the upload below has succeeded)
+    const size_t total = set_tile_layout(ctx, nt);
     std::vector<uint32_t> host(total);
-    for (int m = 1; m <= nt; ++m) build_tile_list(m, host.data() + off[(size_t)m]);
-    {
-        size_t k = tri_total;
-        ctx->band_off.assign((size_t)nt + 1, tri_total);
-        for (int m = 1; m <= nt; ++m) {
-            ctx->band_off[(size_t)m] = k;
-            for (int r = 0; r < m; ++r)
-                for (int c = 0; c < w && c <= r; ++c) host[k++] = (uint32_t)r | ((uint32_t)c << 16);
-        }
-        if (k != total) return set_err(ctx, GAPLAC_E_ARG, "band list size mismatch");
+    for (int m = 1; m <= nt; ++m) {
+        build_tile_list(m, host.data() + ctx->tile_off[(size_t)m]);
+        size_t k = ctx->band_off[(size_t)m];
+        for (int r = 0; r < m; ++r)
+            for (int c = 0; c < ctx->spw && c <= r; ++c) host[k++] = (uint32_t)r | ((uint32_t)c << 16);
     }
     int rc;
     if ((rc = ensure(ctx, &ctx->tiles, &ctx->tiles_elems, total))) return rc;
     HIPCK(ctx, hipMemcpy(ctx->tiles, host.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ctx->tile_off = off;
     ctx->tiles_nt = nt;
     return 0;
 }
@@ -980,41 +1034,17 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     if (ctx->xr_mode == 2)
         launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dXs, ctx->xr_M, ctx->dtp, ctx->gpart,
                          ctx->pmean, ctx->pvar);
-    if (ctx->xr_mode == 1 && ctx->grad_fused && ctx->grad_singletons) {
-        // alpha = Y z first (HBM-bound, ~0.2 ms alone), then M = -C^{-1} tile by tile contracted
-        // in place with every dC/dtheta (cinv_contract_kernel: the tile is never stored nor
-        // read back), then the fixed-order reduction, all on s_main
+    if (ctx->xr_mode == 1) {
+        // Fused (single-term groups): alpha = Y z first (HBM-bound, ~0.2 ms alone), then M =
+        // -C^{-1} tile by tile contracted in place with every dC/dtheta (cinv_contract_kernel:
+        // the tile is never stored nor read back), all on s_main.
+        // Else (or GAPLAC_GRAD_FUSED=0): alpha on s_extra beside M over the factor storage on
+        // s_main (both only read Y; z is copied out first, cinv may overwrite row N), then the
+        // contraction on s_main once alpha is in. Both end in the fixed-order reduction.
+        const bool fused = ctx->grad_fused && ctx->grad_singletons;
         hipStream_t sm = ctx->s_main;
-        launch_zero_tail_cols(sm, ctx->A, lda, Np, N);
-        launch_copy_z(sm, ctx->A, lda, N, ctx->gz);
-        launch_alpha(sm, ctx->A, lda, Np, N, ctx->gz, ctx->gpart, ctx->galpha, ctx->gdv);
-        size_t e0 = 0;
-        const bool ev = ctx->prof_mode == 2;
-        if (ev) {
-            e0 = 2 * ctx->evpairs.size();
-            while (ctx->evpool.size() < e0 + 2) {
-                hipEvent_t e;
-                HIPQ(ctx, hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0], sm));
-        }
-        launch_cinv_contract(sm, ctx->A, lda, Np, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->glist,
-                             ctx->glist_blocks, ctx->gpart, slot(ctx, 8, 0));
-        if (ev) {
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0 + 1], sm));
-            ctx->evpairs.push_back({e0, 0.0, 0.0, 8});
-        }
+        hipStream_t sx = fused || ctx->serial ? sm : ctx->s_extra;  // alpha's stream
         const int m = (int)((N + NB - 1) / NB);
-        launch_grad_reduce(sm, ctx->gpart, m * (m + 1) / 2, ctx->htp->T, ctx->gout);
-        HIPQ(ctx, hipMemcpyAsync(ctx->hgout, ctx->gout, sizeof(double) * (GAPLAC_MAX_TERMS + 1),
-                                  hipMemcpyDeviceToHost, sm));
-    } else if (ctx->xr_mode == 1) {
-        // alpha = Y z on s_extra beside M = -C^{-1} over the factor storage on s_main (both only
-        // read Y; z is copied out first, cinv may overwrite row N), then the contraction and
-        // the reduction on s_main once alpha is in (GAPLAC_GRAD_FUSED=0)
-        hipStream_t sm = ctx->s_main;
-        hipStream_t sx = ctx->serial ? sm : ctx->s_extra;
         launch_zero_tail_cols(sm, ctx->A, lda, Np, N);
         launch_copy_z(sm, ctx->A, lda, N, ctx->gz);
         if (sx != sm) {
@@ -1023,27 +1053,19 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
         }
         launch_alpha(sx, ctx->A, lda, Np, N, ctx->gz, ctx->gpart, ctx->galpha, ctx->gdv);
         if (sx != sm) HIPQ(ctx, hipEventRecord(ctx->ev_xdone, sx));
-        size_t e0 = 0;
-        const bool ev = ctx->prof_mode == 2;
-        if (ev) {
-            e0 = 2 * ctx->evpairs.size();
-            while (ctx->evpool.size() < e0 + 2) {
-                hipEvent_t e;
-                HIPQ(ctx, hipEventCreate(&e));
-                ctx->evpool.push_back(e);
-            }
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0], sm));
+        if ((rc = timed_launch(ctx, ctx->prof_mode == 2, sm, {0, 0.0, 0.0, 8}, [&] {
+                 if (fused)
+                     launch_cinv_contract(sm, ctx->A, lda, Np, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->glist,
+                                          ctx->glist_blocks, ctx->gpart, slot(ctx, 8, 0));
+                 else
+                     launch_cinv_tiles(sm, ctx->A, lda, Np, ctx->glist, ctx->glist_blocks, m, slot(ctx, 8, 0));
+             })))
+            return rc;
+        if (!fused) {
+            if (sx != sm) HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
+            launch_grad_contract(sm, ctx->A, lda, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->dgp, ctx->gpart,
+                                 slot(ctx, 9, 0));
         }
-        launch_cinv_tiles(sm, ctx->A, lda, Np, ctx->glist, ctx->glist_blocks, (int)((N + NB - 1) / NB),
-                          slot(ctx, 8, 0));
-        if (ev) {
-            HIPQ(ctx, hipEventRecord(ctx->evpool[e0 + 1], sm));
-            ctx->evpairs.push_back({e0, 0.0, 0.0, 8});
-        }
-        if (sx != sm) HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-        launch_grad_contract(sm, ctx->A, lda, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->dgp, ctx->gpart,
-                             slot(ctx, 9, 0));
-        const int m = (int)((N + NB - 1) / NB);
         launch_grad_reduce(sm, ctx->gpart, m * (m + 1) / 2, ctx->htp->T, ctx->gout);
         HIPQ(ctx, hipMemcpyAsync(ctx->hgout, ctx->gout, sizeof(double) * (GAPLAC_MAX_TERMS + 1),
                                   hipMemcpyDeviceToHost, sm));
@@ -1075,6 +1097,27 @@ int enqueue_eval(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt) {
     return 0;
 }
 
+// The optional streams (lowest priority, like s_main), created when first wanted and kept:
+// the only creation site besides gaplac_ctx_create's two base streams. Stream budget (a
+// process gets 4 hardware queues by default; streams beyond them share a queue and may
+// serialise behind one another):
+//   plain logpdf context, no split (split_wanted)    2  s_main, s_panel
+//   plain logpdf context at a split size             3  + s_xrest
+//   gradient / posterior context                     4  + s_extra, s_xrest (the measured 79.4 ->
+//                                                       78.0 ms of DESIGN.md §9 had no other stream busy)
+//   two batch lanes (contexts), no split / split     4 / 6
+// The batch lanes were measured at N = 8192 only (no split, 4 streams); no
+// batch-lane measurement at a split size exists.
+int ensure_streams(gaplac_ctx* ctx, bool want_extra, bool want_xrest) {
+    int least = 0, greatest = 0;
+    for (hipStream_t* s : {want_extra ? &ctx->s_extra : nullptr, want_xrest ? &ctx->s_xrest : nullptr}) {
+        if (!s || *s) continue;
+        HIPCK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCK(ctx, hipStreamCreateWithPriority(s, hipStreamNonBlocking, least));
+    }
+    return 0;
+}
+
 // Workspace for order N (grown on demand).
 int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
     const int64_t Np = round_up(N + 1, NB);
@@ -1082,25 +1125,9 @@ int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
     int rc;
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure(ctx, &ctx->A, &ctx->A_elems, (size_t)(Np + (int64_t)NB * ctx->xr_tiles) * Np))) return rc;
-    if (split_wanted(ctx, nt) && !ctx->s_xrest) {
-        // the split bulk updates' second stream (factor_and_reduce): the extra rows' stream
-        // of a gradient / posterior context, idle in a plain evaluation
-        int least = 0, greatest = 0;
-        HIPCK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCK(ctx, hipStreamCreateWithPriority(&ctx->s_xrest, hipStreamNonBlocking, least));
-    }
-    if (ctx->xr_mode && !ctx->s_extra) {
-        // created on first use only: a plain logpdf context keeps two streams, so the
-        // batch lanes (2 contexts) fit the 4 hardware queues a process gets by default. A
-        // gradient / posterior context then holds four streams (s_main, s_panel, s_extra,
-        // s_xrest), all four hardware queues: another context or torch stream in the same
-        // process shares a queue with one of them and may serialise behind it (the
-        // measured 79.4 -> 78.0 ms of DESIGN.md §9 assumes no other streams are busy)
-        int least = 0, greatest = 0;
-        HIPCK(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCK(ctx, hipStreamCreateWithPriority(&ctx->s_extra, hipStreamNonBlocking, least));
-        HIPCK(ctx, hipStreamCreateWithPriority(&ctx->s_xrest, hipStreamNonBlocking, least));
-    }
+    // the extra rows take both optional streams; the split bulk updates of a plain evaluation
+    // (factor_and_reduce) take s_xrest, which would idle there
+    if ((rc = ensure_streams(ctx, ctx->xr_mode != 0, ctx->xr_mode != 0 || split_wanted(ctx, nt)))) return rc;
     if (ctx->xr_mode == 2) {
         const size_t M = (size_t)ctx->xr_M;
         if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, 2 * M * (size_t)((N + 511) / 512)))) return rc;
@@ -1163,7 +1190,7 @@ int eval_device(gaplac_ctx* ctx, int64_t N, int32_t D, const TermPack& tp, EvalR
     const int nt = (int)(Np / NB);
     int rc;
     if ((rc = ensure_workspace(ctx, N))) return rc;
-    const bool prof = ctx->profiling;
+    const bool prof = ctx->prof_mode == 1;
     if (prof) {
         const size_t need = (size_t)nt * 9 + 32;  // launches per evaluation, with margin
         if (ctx->kt_cap < need) {
@@ -1226,29 +1253,18 @@ int finish(const EvalResult& r, double* out_logpdf, double* out_logdet, double* 
     return 0;
 }
 
-int upload(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, const double* v) {
+// The inputs into the context's buffers (ld N), from the host or, for the _device entries,
+// from device memory: a ~N*(D+1)*8-byte D2D copy that keeps the captured graph's pointers fixed.
+int upload(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, const double* v,
+           hipMemcpyKind kind = hipMemcpyHostToDevice) {
     int rc;
     const size_t nx = (size_t)N * (size_t)(D > 0 ? D : 1);
     if ((rc = ensure(ctx, &ctx->dX, &ctx->dX_elems, nx))) return rc;
     if ((rc = ensure(ctx, &ctx->dv, &ctx->dv_elems, (size_t)N))) return rc;
     if (D > 0)
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dX, (size_t)N * 8, X, (size_t)ldx * 8, (size_t)N * 8,
-                                    (size_t)D, hipMemcpyHostToDevice, ctx->s_main));
-    HIPCK(ctx, hipMemcpyAsync(ctx->dv, v, (size_t)N * 8, hipMemcpyHostToDevice, ctx->s_main));
-    return 0;
-}
-
-// Copy device-resident inputs into the context's buffers (ld N): a ~N*(D+1)*8-byte D2D
-// copy that keeps the captured graph's pointers fixed.
-int upload_device(gaplac_ctx* ctx, int64_t N, int32_t D, const double* dX, int64_t ldx, const double* dv) {
-    int rc;
-    const size_t nx = (size_t)N * (size_t)(D > 0 ? D : 1);
-    if ((rc = ensure(ctx, &ctx->dX, &ctx->dX_elems, nx))) return rc;
-    if ((rc = ensure(ctx, &ctx->dv, &ctx->dv_elems, (size_t)N))) return rc;
-    if (D > 0)
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dX, (size_t)N * 8, dX, (size_t)ldx * 8, (size_t)N * 8,
-                                    (size_t)D, hipMemcpyDeviceToDevice, ctx->s_main));
-    HIPCK(ctx, hipMemcpyAsync(ctx->dv, dv, (size_t)N * 8, hipMemcpyDeviceToDevice, ctx->s_main));
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dX, (size_t)N * 8, X, (size_t)ldx * 8, (size_t)N * 8, (size_t)D, kind,
+                                    ctx->s_main));
+    HIPCK(ctx, hipMemcpyAsync(ctx->dv, v, (size_t)N * 8, kind, ctx->s_main));
     return 0;
 }
 
@@ -1256,6 +1272,29 @@ void nan_out(double* a, double* b, double* c) {
     if (a) *a = NAN;
     if (b) *b = NAN;
     if (c) *c = NAN;
+}
+
+// Shared body of gaplac_logpdf / _device.
+int logpdf_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                const gaplac_term* terms, double noise, const double* v, double* out_logpdf, double* out_logdet,
+                double* out_quad) {
+    nan_out(out_logpdf, out_logdet, out_quad);
+    int rc = check_common(ctx, N, D, X, ldx, noise, v);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (N == 0) {  // logpdf of an empty FiniteGP: -(0 + 0 + 0)/2
+        if (out_logpdf) *out_logpdf = -0.0;
+        if (out_logdet) *out_logdet = 0.0;
+        if (out_quad) *out_quad = 0.0;
+        return 0;
+    }
+    tp.noise = noise;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, N, D, X, ldx, v, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
+    EvalResult r;
+    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    return finish(r, out_logpdf, out_logdet, out_quad);
 }
 
 // Shared body of gaplac_logpdf_grad / _device.
@@ -1290,7 +1329,7 @@ int logpdf_grad_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, cons
     ctx->grad_singletons = true;
     for (int t = 0; t < T; ++t) ctx->grad_singletons = ctx->grad_singletons && gp.gend[t] - gp.gstart[t] == 1;
     HIPCK(ctx, hipSetDevice(ctx->device));
-    if ((rc = on_device ? upload_device(ctx, N, D, X, ldx, v) : upload(ctx, N, D, X, ldx, v))) return rc;
+    if ((rc = upload(ctx, N, D, X, ldx, v, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     tp.noise = noise;
     *ctx->hgp = gp;
     HIPCK(ctx, hipMemcpyAsync(ctx->dgp, ctx->hgp, sizeof(GradTermPack), hipMemcpyHostToDevice, ctx->s_main));
@@ -1393,8 +1432,6 @@ static int batch_tail_enqueue(gaplac_ctx* ctx, int64_t N, const std::vector<Term
     if ((rc = ensure(ctx, &w.dres, &w.dres_elems, (size_t)B))) return rc;
     if ((rc = ensure(ctx, &w.dtp, &w.dtp_elems, (size_t)B))) return rc;
     if ((rc = ensure(ctx, &w.ctl, &w.ctl_elems, (size_t)B))) return rc;
-    if (!w.ev_gram) HIPCK(ctx, hipEventCreateWithFlags(&w.ev_gram, hipEventDisableTiming));
-    if (!w.ev_done) HIPCK(ctx, hipEventCreateWithFlags(&w.ev_done, hipEventDisableTiming));
     if (w.host_cap < B) {
         if (w.hres) (void)hipHostFree(w.hres);
         if (w.htp) (void)hipHostFree(w.htp);
@@ -1498,6 +1535,44 @@ static int batch_tail_finish(gaplac_ctx* ctx, int p, double* out_logpdf, int64_t
     return 0;
 }
 
+// A host-only walk of one evaluation's schedule (both plan checks): c, a context on the
+// stack with its switches and extra-row mode set, gets the workspace size and tile layout
+// ensure_workspace would give it for order N behind a fake pointer (never dereferenced:
+// the walk only does pointer arithmetic against the guard's base), and the schedule is
+// enqueued dry under g, whose workspace is short_by elements short (the negative control).
+static int dry_walk(gaplac_ctx& c, int64_t N, LaunchGuard& g, int64_t short_by = 0) {
+    const int64_t Np = round_up(N + 1, NB);
+    const int nt = (int)(Np / NB);
+    double* const fake = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    TermPack tp{};
+    tp.T = 1;
+    c.dry = true;
+    c.tail_s = 80;  // as gaplac_ctx_create sets it with the persistent tail
+    c.A = c.Dinv = fake;
+    c.A_elems = (size_t)(Np + (int64_t)NB * c.xr_tiles) * (size_t)Np;
+    c.tiles = reinterpret_cast<uint32_t*>(fake);
+    c.htp = &tp;
+    set_tile_layout(&c, nt);
+    c.tiles_nt = nt;
+    if (c.xr_mode == 1) {
+        std::vector<uint32_t> gl;
+        build_grad_list((int)((N + NB - 1) / NB), gl);
+        c.glist_blocks = (int)gl.size();
+    }
+    g.base = fake;
+    g.elems = (int64_t)c.A_elems - short_by;
+    g.dry = true;
+    int rc;
+    {
+        GuardScope scope(&g);
+        rc = enqueue_eval(&c, N, 1, Np, nt);
+    }
+    c.htp = nullptr;  // nothing of the walk's stays behind in c
+    c.A = c.Dinv = nullptr;
+    c.tiles = nullptr;
+    return rc;
+}
+
 extern "C" {
 
 int gaplac_abi_version(void) { return GAPLAC_ABI_VERSION; }
@@ -1557,47 +1632,11 @@ int gaplac_ctx_create(int device, gaplac_ctx** out) {
         return fail("stream", e);
     if ((e = hipStreamCreateWithPriority(&ctx->s_main, hipStreamNonBlocking, least)) != hipSuccess)
         return fail("stream", e);
-    for (int q = 0; q < 2; ++q) {
-        if ((e = hipEventCreateWithFlags(&ctx->ev_P[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-        if ((e = hipEventCreateWithFlags(&ctx->ev_R[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-        if ((e = hipEventCreateWithFlags(&ctx->ev_xc[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-        if ((e = hipEventCreateWithFlags(&ctx->ev_xr[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-    }
-    if ((e = hipEventCreateWithFlags(&ctx->ev_gram, hipEventDisableTiming)) != hipSuccess)
-        return fail("event", e);
-    for (int q = 0; q < 2; ++q) {
-        if ((e = hipEventCreateWithFlags(&ctx->ev_split[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-        if ((e = hipEventCreateWithFlags(&ctx->ev_rest[q], hipEventDisableTiming)) != hipSuccess)
-            return fail("event", e);
-    }
-    if ((e = hipEventCreateWithFlags(&ctx->ev_gram2, hipEventDisableTiming)) != hipSuccess)
-        return fail("event", e);
-    if ((e = hipEventCreateWithFlags(&ctx->ev_xinit, hipEventDisableTiming)) != hipSuccess)
-        return fail("event", e);
-    if ((e = hipEventCreateWithFlags(&ctx->ev_xdone, hipEventDisableTiming)) != hipSuccess)
-        return fail("event", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->dres), sizeof(EvalResult))) != hipSuccess)
-        return fail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->hres), sizeof(EvalResult), 0)) != hipSuccess)
-        return fail("hipHostMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->dtp), sizeof(TermPack))) != hipSuccess)
-        return fail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->htp), sizeof(TermPack), 0)) != hipSuccess)
-        return fail("hipHostMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->gout), sizeof(double) * (GAPLAC_MAX_TERMS + 1))) != hipSuccess)
-        return fail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->hgout), sizeof(double) * (GAPLAC_MAX_TERMS + 1), 0)) !=
-        hipSuccess)
-        return fail("hipHostMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->dgp), sizeof(GradTermPack))) != hipSuccess)
-        return fail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->hgp), sizeof(GradTermPack), 0)) != hipSuccess)
-        return fail("hipHostMalloc", e);
+    for (hipEvent_t* ev : ctx_events(ctx))
+        if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return fail("event", e);
+    for (const Buf& b : ctx_buffers(ctx))
+        if (b.fixed && (e = b.pinned ? hipHostMalloc(b.p, b.fixed, 0) : hipMalloc(b.p, b.fixed)) != hipSuccess)
+            return fail(b.pinned ? "hipHostMalloc" : "hipMalloc", e);
     *out = ctx;
     return 0;
 }
@@ -1605,73 +1644,18 @@ int gaplac_ctx_create(int device, gaplac_ctx** out) {
 int gaplac_ctx_destroy(gaplac_ctx* ctx) {
     if (!ctx) return 0;
     (void)hipSetDevice(ctx->device);
-    if (ctx->s_main) (void)hipStreamSynchronize(ctx->s_main);
-    if (ctx->s_panel) (void)hipStreamSynchronize(ctx->s_panel);
-    if (ctx->s_extra) (void)hipStreamSynchronize(ctx->s_extra);
-    if (ctx->s_xrest) (void)hipStreamSynchronize(ctx->s_xrest);
+    (void)sync_streams(ctx);
     for (gaplac_ctx* c : ctx->lanes) gaplac_ctx_destroy(c);
-    ctx->lanes.clear();
     if (ctx->borrowed_inputs) {
         ctx->dX = nullptr;
         ctx->dv = nullptr;
     }
-    for (int q = 0; q < 2; ++q) {
-        if (ctx->ev_P[q]) (void)hipEventDestroy(ctx->ev_P[q]);
-        if (ctx->ev_R[q]) (void)hipEventDestroy(ctx->ev_R[q]);
-        if (ctx->ev_xc[q]) (void)hipEventDestroy(ctx->ev_xc[q]);
-        if (ctx->ev_xr[q]) (void)hipEventDestroy(ctx->ev_xr[q]);
-    }
-    if (ctx->ev_gram) (void)hipEventDestroy(ctx->ev_gram);
-    if (ctx->ev_gram2) (void)hipEventDestroy(ctx->ev_gram2);
-    for (int q = 0; q < 2; ++q) {
-        if (ctx->ev_split[q]) (void)hipEventDestroy(ctx->ev_split[q]);
-        if (ctx->ev_rest[q]) (void)hipEventDestroy(ctx->ev_rest[q]);
-    }
-    if (ctx->ev_xinit) (void)hipEventDestroy(ctx->ev_xinit);
-    if (ctx->ev_xdone) (void)hipEventDestroy(ctx->ev_xdone);
-    if (ctx->A) (void)hipFree(ctx->A);
-    if (ctx->Dinv) (void)hipFree(ctx->Dinv);
-    if (ctx->tiles) (void)hipFree(ctx->tiles);
-    if (ctx->dX) (void)hipFree(ctx->dX);
-    if (ctx->dv) (void)hipFree(ctx->dv);
+    for (hipEvent_t* ev : ctx_events(ctx))
+        if (*ev) (void)hipEventDestroy(*ev);
     for (hipEvent_t e : ctx->evpool) (void)hipEventDestroy(e);
-    if (ctx->dkt) (void)hipFree(ctx->dkt);
-    if (ctx->hkt) (void)hipHostFree(ctx->hkt);
-    if (ctx->galpha) (void)hipFree(ctx->galpha);
-    if (ctx->dXs) (void)hipFree(ctx->dXs);
-    if (ctx->pmean) (void)hipFree(ctx->pmean);
-    if (ctx->pvar) (void)hipFree(ctx->pvar);
-    if (ctx->gdv) (void)hipFree(ctx->gdv);
-    if (ctx->gz) (void)hipFree(ctx->gz);
-    if (ctx->gpart) (void)hipFree(ctx->gpart);
-    if (ctx->gout) (void)hipFree(ctx->gout);
-    if (ctx->hgout) (void)hipHostFree(ctx->hgout);
-    if (ctx->dgp) (void)hipFree(ctx->dgp);
-    if (ctx->hgp) (void)hipHostFree(ctx->hgp);
-    if (ctx->glist) (void)hipFree(ctx->glist);
-    if (ctx->tctl) (void)hipFree(ctx->tctl);
-    for (auto& w : ctx->bw) {
-        if (w.A) (void)hipFree(w.A);
-        if (w.Dinv) (void)hipFree(w.Dinv);
-        if (w.dres) (void)hipFree(w.dres);
-        if (w.dtp) (void)hipFree(w.dtp);
-        if (w.hres) (void)hipHostFree(w.hres);
-        if (w.htp) (void)hipHostFree(w.htp);
-        if (w.ctl) (void)hipFree(w.ctl);
-        if (w.tasks) (void)hipFree(w.tasks);
-        if (w.ev_gram) (void)hipEventDestroy(w.ev_gram);
-        if (w.ev_done) (void)hipEventDestroy(w.ev_done);
-    }
-    if (ctx->ttasks) (void)hipFree(ctx->ttasks);
-    if (ctx->ttrace) (void)hipFree(ctx->ttrace);
-    if (ctx->dres) (void)hipFree(ctx->dres);
-    if (ctx->dtp) (void)hipFree(ctx->dtp);
-    if (ctx->htp) (void)hipHostFree(ctx->htp);
-    if (ctx->hres) (void)hipHostFree(ctx->hres);
-    if (ctx->s_main) (void)hipStreamDestroy(ctx->s_main);
-    if (ctx->s_panel) (void)hipStreamDestroy(ctx->s_panel);
-    if (ctx->s_extra) (void)hipStreamDestroy(ctx->s_extra);
-    if (ctx->s_xrest) (void)hipStreamDestroy(ctx->s_xrest);
+    for (const Buf& b : ctx_buffers(ctx)) free_buf(b);
+    for (hipStream_t s : {ctx->s_main, ctx->s_panel, ctx->s_extra, ctx->s_xrest})
+        if (s) (void)hipStreamDestroy(s);
     delete ctx;
     return 0;
 }
@@ -1679,70 +1663,28 @@ int gaplac_ctx_destroy(gaplac_ctx* ctx) {
 int gaplac_ctx_release(gaplac_ctx* ctx) {
     if (!ctx) return GAPLAC_E_ARG;
     HIPCK(ctx, hipSetDevice(ctx->device));
-    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
-    HIPCK(ctx, hipStreamSynchronize(ctx->s_panel));
-    if (ctx->s_extra) HIPCK(ctx, hipStreamSynchronize(ctx->s_extra));
-    if (ctx->s_xrest) HIPCK(ctx, hipStreamSynchronize(ctx->s_xrest));
+    HIPCK(ctx, sync_streams(ctx));
     for (gaplac_ctx* c : ctx->lanes) gaplac_ctx_destroy(c);
     ctx->lanes.clear();
-    auto drop = [](double*& p, size_t& n) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    };
-    drop(ctx->A, ctx->A_elems);
-    drop(ctx->Dinv, ctx->Dinv_elems);
     for (auto& w : ctx->bw) {
         if (w.busy) HIPCK(ctx, hipEventSynchronize(w.ev_done));
         w.busy = false;
-        drop(w.A, w.A_elems);
-        drop(w.Dinv, w.Dinv_elems);
     }
+    for (const Buf& b : ctx_buffers(ctx))
+        if (b.cap) free_buf(b);  // the large ones: the matrices and their diagonal inverses
     return 0;
 }
 
 int gaplac_logpdf_device(gaplac_ctx* ctx, int64_t N, int32_t D, const double* dX, int64_t ldx,
                          int32_t T, const gaplac_term* terms, double noise, const double* dv,
                          double* out_logpdf, double* out_logdet, double* out_quad) {
-    nan_out(out_logpdf, out_logdet, out_quad);
-    int rc = check_common(ctx, N, D, dX, ldx, noise, dv);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (N == 0) {  // logpdf of an empty FiniteGP: -(0 + 0 + 0)/2
-        if (out_logpdf) *out_logpdf = -0.0;
-        if (out_logdet) *out_logdet = 0.0;
-        if (out_quad) *out_quad = 0.0;
-        return 0;
-    }
-    tp.noise = noise;
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload_device(ctx, N, D, dX, ldx, dv))) return rc;
-    EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
-    return finish(r, out_logpdf, out_logdet, out_quad);
+    return logpdf_impl(ctx, true, N, D, dX, ldx, T, terms, noise, dv, out_logpdf, out_logdet, out_quad);
 }
 
 int gaplac_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                   const gaplac_term* terms, double noise, const double* v, double* out_logpdf,
                   double* out_logdet, double* out_quad) {
-    nan_out(out_logpdf, out_logdet, out_quad);
-    int rc = check_common(ctx, N, D, X, ldx, noise, v);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (N == 0) {
-        if (out_logpdf) *out_logpdf = -0.0;
-        if (out_logdet) *out_logdet = 0.0;
-        if (out_quad) *out_quad = 0.0;
-        return 0;
-    }
-    HIPCK(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload(ctx, N, D, X, ldx, v))) return rc;
-    tp.noise = noise;
-    EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
-    return finish(r, out_logpdf, out_logdet, out_quad);
+    return logpdf_impl(ctx, false, N, D, X, ldx, T, terms, noise, v, out_logpdf, out_logdet, out_quad);
 }
 
 int gaplac_logpdf_batch(gaplac_ctx* ctx, int32_t nmodels, int64_t N, int32_t D, const double* X,
@@ -1869,13 +1811,7 @@ int gaplac_logpdf_batch(gaplac_ctx* ctx, int32_t nmodels, int64_t N, int32_t D, 
     // on an error, wait for every lane still in flight before returning: they read the
     // borrowed dX / dv, which the next call's upload overwrites
     auto quiesce = [&](int code) -> int {
-        for (int l = 0; l < nl; ++l) {
-            gaplac_ctx* c = lane[(size_t)l];
-            (void)hipStreamSynchronize(c->s_main);
-            (void)hipStreamSynchronize(c->s_panel);
-            if (c->s_extra) (void)hipStreamSynchronize(c->s_extra);
-            if (c->s_xrest) (void)hipStreamSynchronize(c->s_xrest);
-        }
+        for (int l = 0; l < nl; ++l) (void)sync_streams(lane[(size_t)l]);
         return code;
     };
     for (int m = 0; m < nmodels; ++m) {
@@ -2058,39 +1994,6 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
     const bool short_ws = mode >= 8;  // negative control: a workspace one element short
     if (short_ws) mode -= 8;
     if (N < 1 || mode < 0 || mode > 2 || (mode == 2 && M < 1) || spw < 1 || spw > 8) return GAPLAC_E_ARG;
-    gaplac_ctx c;
-    c.dry = true;
-    c.spw = spw;
-    const int64_t Np = round_up(N + 1, NB);
-    const int nt = (int)(Np / NB);
-    c.xr_mode = mode;
-    c.xr_tiles = mode == 1 ? nt : mode == 2 ? (int)((M + NB - 1) / NB) : 0;
-    c.xr_M = mode == 2 ? M : 0;
-    // never dereferenced: the walk only does pointer arithmetic against the guard's base
-    double* const fake = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    c.A = fake;
-    c.A_elems = (size_t)(Np + (int64_t)NB * c.xr_tiles) * (size_t)Np;  // as ensure_workspace
-    c.Dinv = fake;
-    c.tiles = reinterpret_cast<uint32_t*>(fake);
-    c.tile_off.assign((size_t)nt + 1, 0);
-    for (int m = 1; m <= nt; ++m) c.tile_off[(size_t)m] = c.tile_off[(size_t)m - 1] + (size_t)(m - 1) * m / 2;
-    c.tiles_nt = nt;
-    // band list offsets as ensure_tile_lists lays them out (the walk launches the same bands)
-    c.band_off.assign((size_t)nt + 1, 0);
-    {
-        size_t k = c.tile_off[(size_t)nt] + (size_t)nt * (nt + 1) / 2;
-        for (int m = 1; m <= nt; ++m) {
-            c.band_off[(size_t)m] = k;
-            const size_t w = (size_t)std::min(c.spw, m);
-            k += w * m - w * (w - 1) / 2;
-        }
-    }
-    if (mode == 1) {
-        std::vector<uint32_t> gl;
-        build_grad_list((int)((N + NB - 1) / NB), gl);
-        c.glist_blocks = (int)gl.size();
-    }
-    c.tail_s = 80;  // as gaplac_ctx_create sets it with the persistent tail
     {
         // every tail length the library can launch: the task list is a topological order
         static std::string tail_bad = [] {
@@ -2157,22 +2060,13 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
             return GAPLAC_E_ARG;
         }
     }
-    TermPack tp{};
-    tp.T = 1;
-    c.htp = &tp;
+    gaplac_ctx c;
+    c.spw = spw;
+    c.xr_mode = mode;
+    c.xr_tiles = mode == 1 ? (int)(round_up(N + 1, NB) / NB) : mode == 2 ? (int)((M + NB - 1) / NB) : 0;
+    c.xr_M = mode == 2 ? M : 0;
     LaunchGuard g;
-    g.base = fake;
-    g.elems = (int64_t)c.A_elems - (short_ws ? 1 : 0);
-    g.dry = true;
-    int rc;
-    {
-        GuardScope scope(&g);
-        rc = enqueue_eval(&c, N, 1, Np, nt);
-    }
-    c.htp = nullptr;
-    c.A = nullptr;
-    c.Dinv = nullptr;
-    c.tiles = nullptr;
+    const int rc = dry_walk(c, N, g, short_ws ? 1 : 0);
     if (out_launches) *out_launches = g.launches;
     if (out_violations) *out_violations = g.violations;
     if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
@@ -2191,49 +2085,15 @@ int gaplac_plan_check_schedule(int64_t N, int32_t spw, int32_t depth, int32_t pa
     if (N < 1 || spw < 1 || spw > 8 || depth < 0 || depth > 8 || pair_ext < 0 || pair_ext > 1 || pair_m < 0)
         return GAPLAC_E_ARG;
     gaplac_ctx c;
-    c.dry = true;
     c.spw = spw;
     c.pair_depth = depth;
     c.pair_ext = pair_ext;
     c.pair_m = pair_m;
-    const int64_t Np = round_up(N + 1, NB);
-    const int nt = (int)(Np / NB);
-    double* const fake = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    c.A = fake;
-    c.A_elems = (size_t)Np * (size_t)Np;
-    c.Dinv = fake;
-    c.tiles = reinterpret_cast<uint32_t*>(fake);
-    c.tile_off.assign((size_t)nt + 1, 0);
-    for (int m = 1; m <= nt; ++m) c.tile_off[(size_t)m] = c.tile_off[(size_t)m - 1] + (size_t)(m - 1) * m / 2;
-    c.tiles_nt = nt;
-    c.band_off.assign((size_t)nt + 1, 0);
-    {
-        size_t k = c.tile_off[(size_t)nt] + (size_t)nt * (nt + 1) / 2;
-        for (int m = 1; m <= nt; ++m) {
-            c.band_off[(size_t)m] = k;
-            const size_t w = (size_t)std::min(c.spw, m);
-            k += w * m - w * (w - 1) / 2;
-        }
-    }
-    c.tail_s = 80;
-    TermPack tp{};
-    tp.T = 1;
-    c.htp = &tp;
+    const int nt = (int)(round_up(N + 1, NB) / NB);
     LaunchGuard g;
-    g.base = fake;
-    g.elems = (int64_t)c.A_elems;
-    g.dry = true;
     std::vector<int> acct;
     g.acct = &acct;
-    int rc;
-    {
-        GuardScope scope(&g);
-        rc = enqueue_eval(&c, N, 1, Np, nt);
-    }
-    c.htp = nullptr;
-    c.A = nullptr;
-    c.Dinv = nullptr;
-    c.tiles = nullptr;
+    const int rc = dry_walk(c, N, g);
     std::string why;
     char b[200];
     if (rc) why = "the dry walk failed";
@@ -2290,7 +2150,6 @@ int gaplac_plan_check_schedule(int64_t N, int32_t spw, int32_t depth, int32_t pa
 int gaplac_set_profiling(gaplac_ctx* ctx, int mode) {
     if (!ctx || mode < 0 || mode > 2) return GAPLAC_E_ARG;
     ctx->prof_mode = mode;
-    ctx->profiling = mode == 1;
     return 0;
 }
 
@@ -2298,11 +2157,13 @@ int gaplac_get_stats(gaplac_ctx* ctx, gaplac_stats* out) {
     if (!ctx || !out) return GAPLAC_E_ARG;
     if (!ctx->evpairs.empty()) {  // fold the event-timed bulk launches in
         HIPCK(ctx, hipSetDevice(ctx->device));
-        HIPCK(ctx, hipDeviceSynchronize());  // (events on s_main, s_panel and the split's s_xrest)
         std::vector<std::pair<double, double>> iv;  // bulk-type launch intervals, ms after the first event
         const hipEvent_t ref = ctx->evpool[ctx->evpairs.front().i0];
         for (const auto& p : ctx->evpairs) {
             float ms = 0.f;
+            // (the pair's launch retired: pairs lie on s_main, s_panel and the split's s_xrest,
+            // each stream in order, so no other stream or context is waited for)
+            HIPCK(ctx, hipEventSynchronize(ctx->evpool[p.i0 + 1]));
             HIPCK(ctx, hipEventElapsedTime(&ms, ctx->evpool[p.i0], ctx->evpool[p.i0 + 1]));
             if (p.kind == 8) {
                 ctx->stats.cinv_ms += ms;
