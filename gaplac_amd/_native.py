@@ -32,6 +32,9 @@ EXPORTED = (
     "gaplac_logpdf_grad_device",
     "gaplac_posterior_mean_var",
     "gaplac_rand",
+    "gaplac_logpdf_multi",
+    "gaplac_logpdf_multi_device",
+    "gaplac_rand_multi",
     "gaplac_gram",
     "gaplac_gram_time",
     "gaplac_factor",
@@ -149,6 +152,11 @@ def load() -> ctypes.CDLL:
     lib.gaplac_logpdf_grad_device.argtypes = common + [_DP, c_void_p, c_void_p, _DP]
     lib.gaplac_posterior_mean_var.argtypes = common + [c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.gaplac_rand.argtypes = common + [c_void_p]
+    # (the matrix forms take R, the matrix and its leading dimension where `common` ends in v)
+    multi = common[:-1] + [c_int64, c_void_p, c_int64]
+    lib.gaplac_logpdf_multi.argtypes = multi + [c_void_p, _DP, c_void_p]
+    lib.gaplac_logpdf_multi_device.argtypes = multi + [c_void_p, _DP, c_void_p]
+    lib.gaplac_rand_multi.argtypes = multi + [c_void_p, c_int64]
     lib.gaplac_gram.argtypes = [
         c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Term), c_double, c_void_p, c_int64,
     ]

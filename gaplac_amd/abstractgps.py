@@ -71,12 +71,16 @@ class FiniteGP:
 
 def logpdf(fx: FiniteGP, y, ctx: backend.Context | None = None, full: bool = False):
     """-(N log 2pi + logdet(C) + ||U^-T y||^2) / 2 on the GPU; raises
-    backend.PosDefException(info) when C is not positive definite (cholesky check=true)."""
+    backend.PosDefException(info) when C is not positive definite (cholesky check=true).
+    A matrix y (N x R) is AbstractGPs' logpdf(fx, Y::AbstractMatrix): one log-density per
+    column, shape (R,), from one factorisation (gaplac_logpdf_multi)."""
     _gate()
     ctx = ctx or backend.default_context()
     y = np.asarray(y, dtype=np.float64)
-    if y.shape[0] != len(fx):
+    if y.ndim == 0 or y.shape[0] != len(fx):
         raise F.ArgumentError("DimensionMismatch: length of y does not match the FiniteGP")
+    if y.ndim == 2:
+        return ctx.logpdf_multi(fx.x, fx.terms, fx.noise, y, full=full)
     return ctx.logpdf(fx.x, fx.terms, fx.noise, y, full=full)
 
 
@@ -135,15 +139,22 @@ def mean_and_var(f: PosteriorGP, x):
     return f.mean_and_var(x)
 
 
-def rand(fx: FiniteGP, z=None, rng=None, ctx: backend.Context | None = None):
+def rand(fx: FiniteGP, n=None, z=None, rng=None, ctx: backend.Context | None = None):
     """rand(rng, fx) = cholesky(C).U' * randn(rng, N) for the zero-mean FiniteGP
     (CLI/src/sample.jl:25). The standard-normal draws stay on the host: pass z, or an rng
-    (numpy Generator) to draw it."""
+    (numpy Generator) to draw it.
+    With n (or a 2-D z, N x n) it is rand(rng, fx, n::Int) = cholesky(C).U' * randn(rng, N, n):
+    an N x n matrix from one factorisation (gaplac_rand_multi), the draws made as
+    rng.standard_normal((N, n))."""
     _gate()
     ctx = ctx or backend.default_context()
+    if n is not None and z is not None and (np.ndim(z) != 2 or np.shape(z)[1] != int(n)):
+        raise F.ArgumentError("DimensionMismatch: z must be N x n when both n and z are given")
     if z is None:
         rng = rng if rng is not None else np.random.default_rng()
-        z = rng.standard_normal(len(fx))
+        z = rng.standard_normal(len(fx) if n is None else (len(fx), int(n)))
+    if np.ndim(z) == 2:
+        return ctx.rand_multi(fx.x, fx.terms, fx.noise, z)
     return ctx.rand(fx.x, fx.terms, fx.noise, z)
 
 
@@ -167,13 +178,28 @@ def design_matrix(table, vars_) -> np.ndarray:
     return np.column_stack(cols)
 
 
-def select_formulae(f1: str, f2: str, table, noise: float = 0.1, ctx: backend.Context | None = None):
+def select_formulae(f1: str, f2: str, table, noise: float = 0.1, ctx: backend.Context | None = None,
+                    responses=None):
     """CLI/src/select.jl:21-54 (`select --formulae`): logpdf of two formulas on the same
     data and the printed "Log2 Bayes" value, which is lp1 - lp2. Both models
-    run through one batched call."""
+    run through one batched call.
+    responses: a list of column names scored in place of the formulas' own response (one
+    covariate table, many responses): each formula is factored once and scored against all of
+    them (two logpdf_multi calls); the three results are then arrays, one entry per name."""
     _gate()
     ctx = ctx or backend.default_context()
     specs = [F.gp_spec(f1), F.gp_spec(f2)]
+    if responses is not None:
+        names = list(responses)
+        Y = np.column_stack([np.asarray(table[r], dtype=np.float64) for r in names]) if names else None
+        lps = []
+        for s in specs:
+            gp, vars_ = make_gp(s)
+            X = design_matrix(table, vars_)
+            Ys = Y if Y is not None else np.zeros((X.shape[0], 0))
+            lps.append(logpdf(FiniteGP(gp, X, noise), Ys, ctx=ctx))
+        lp1, lp2 = lps
+        return lp1 - lp2, lp1, lp2
     if F.response(specs[0]) != F.response(specs[1]):
         # the reference reads each response separately; keep the same data flow
         pass

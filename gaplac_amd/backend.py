@@ -213,6 +213,72 @@ class Context:
         self._check(rc)
         return out
 
+    def _multi_outputs(self, R: int):
+        lp = np.empty(max(R, 1), dtype=np.float64)
+        q = np.empty(max(R, 1), dtype=np.float64)
+        return lp, c_double(0.0), q
+
+    def logpdf_multi(self, X, terms, noise: float, Y, full: bool = False):
+        """logpdf of every column of Y (N x R) under the zero-mean FiniteGP, one factorisation
+        (gaplac_logpdf_multi): an array of R, or (logpdf[R], logdet, quad[R]) with full=True."""
+        Xc = _colmajor(X)
+        Yc = np.asarray(Y, dtype=np.float64)
+        if Yc.ndim != 2:
+            raise ArgumentError(f"Y must be a matrix (N x R), got {Yc.ndim} dimension(s)")
+        Yc = np.asfortranarray(Yc)
+        N, D = Xc.shape
+        if Yc.shape[0] != N:
+            raise ArgumentError(f"rows of Y ({Yc.shape[0]}) != N ({N})")
+        R = Yc.shape[1]
+        terms = list(terms)
+        ta = term_array(terms)
+        lp, ld, q = self._multi_outputs(R)
+        rc = self.lib.gaplac_logpdf_multi(
+            self.h, N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+            R, Yc.ctypes.data_as(c_void_p), max(N, 1), lp.ctypes.data_as(c_void_p), byref(ld),
+            q.ctypes.data_as(c_void_p),
+        )
+        self._check(rc)
+        return (lp[:R], ld.value, q[:R]) if full else lp[:R]
+
+    def logpdf_multi_device(self, N: int, D: int, dX_ptr: int, ldx: int, terms, noise: float, R: int, dY_ptr: int,
+                            ldy: int, full: bool = False):
+        """Device-resident X (N x D, ldx) and Y (N x R, ldy); the results are host arrays."""
+        terms = list(terms)
+        ta = term_array(terms)
+        if R < 0:
+            raise ArgumentError(f"R = {R} < 0")
+        lp, ld, q = self._multi_outputs(R)
+        rc = self.lib.gaplac_logpdf_multi_device(
+            self.h, N, D, c_void_p(dX_ptr), ldx, len(terms), ta, float(noise), R, c_void_p(dY_ptr), ldy,
+            lp.ctypes.data_as(c_void_p), byref(ld), q.ctypes.data_as(c_void_p),
+        )
+        self._check(rc)
+        return (lp[:R], ld.value, q[:R]) if full else lp[:R]
+
+    def rand_multi(self, X, terms, noise: float, Z):
+        """L Z with C = K(X) + noise I = L L^T (gaplac_rand_multi): one draw of the FiniteGP per
+        column of the standard-normal matrix Z (N x R). Returns N x R (column-major)."""
+        Xc = _colmajor(X)
+        Zc = np.asarray(Z, dtype=np.float64)
+        if Zc.ndim != 2:
+            raise ArgumentError(f"Z must be a matrix (N x R), got {Zc.ndim} dimension(s)")
+        Zc = np.asfortranarray(Zc)
+        N, D = Xc.shape
+        if Zc.shape[0] != N:
+            raise ArgumentError(f"rows of Z ({Zc.shape[0]}) != N ({N})")
+        R = Zc.shape[1]
+        terms = list(terms)
+        ta = term_array(terms)
+        out = np.empty((N, R), dtype=np.float64, order="F")
+        buf = out if out.size else np.empty(1)  # (an empty result still passes a valid pointer)
+        rc = self.lib.gaplac_rand_multi(
+            self.h, N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+            R, Zc.ctypes.data_as(c_void_p), max(N, 1), buf.ctypes.data_as(c_void_p), max(N, 1),
+        )
+        self._check(rc)
+        return out
+
     def gram(self, X, terms, noise: float = 0.0) -> np.ndarray:
         Xc = _colmajor(X)
         N, D = Xc.shape

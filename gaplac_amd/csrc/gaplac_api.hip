@@ -153,11 +153,24 @@ struct gaplac_ctx {
     // Extra rows below the matrix, factored along (lda = Np + 128 xr_tiles):
     //   1 = identity rows E = [I 0] -> L^{-T} (gradient, gaplac_logpdf_grad)
     //   2 = K(xs, X) -> (L^{-1} K(X, xs))^T (posterior, gaplac_posterior_mean_var, §10)
+    //   3 = Y^T -> (L^{-1} Y)^T (the responses of gaplac_logpdf_multi, §10.5)
+    // Modes 2 and 3 are dense rows (dense_rows): one schedule for both.
     int xr_mode = 0;
     int xr_tiles = 0;
-    int64_t xr_M = 0;       // mode 2: test points
+    int64_t xr_M = 0;       // mode 2: test points; mode 3: responses R
     double* dXs = nullptr;  // mode 2: test inputs (ld M)
     size_t dXs_elems = 0;
+    const double* xr_Y = nullptr;  // mode 3: the responses on the device (dY, or the caller's matrix), ld xr_ldy
+    int64_t xr_ldy = 0;
+    double* dY = nullptr;  // gaplac_logpdf_multi: the host matrix's copy (ld N)
+    size_t dY_elems = 0;
+    double* mres = nullptr;  // mode 3 results: quad[R], then logpdf[R]
+    size_t mres_elems = 0;
+    // gaplac_rand_multi: Z (ld Np, so the kernel's 16-byte loads are aligned) and OUT (ld N)
+    double* dZ = nullptr;
+    size_t dZ_elems = 0;
+    double* dO = nullptr;
+    size_t dO_elems = 0;
     double* pmean = nullptr;
     double* pvar = nullptr;
     size_t pmv_elems = 0;
@@ -241,7 +254,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        buf(&c->ttasks), buf(&c->ttrace), buf(&c->dkt), buf(&c->hkt, 0, true), buf(&c->dXs),
                        buf(&c->pmean), buf(&c->pvar), buf(&c->galpha), buf(&c->gdv), buf(&c->gz), buf(&c->gpart),
                        buf(&c->gout, gout_bytes), buf(&c->hgout, gout_bytes, true), buf(&c->dgp, sizeof(GradTermPack)),
-                       buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist)};
+                       buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist), large(&c->dY, &c->dY_elems),
+                       buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -545,11 +559,15 @@ static void extra_rows_update(gaplac_ctx* ctx, hipStream_t sm, int64_t lda, int 
 // most tail_s tile columns after it; those columns are factored by serial_tail().
 // The whole matrix in the persistent tail (no super-panels): plain logpdf with at most
 // tail_s (and TAIL_TMAX) tile columns.
-// Which evaluations take a tail: plain logpdf, and the posterior when its cross-covariance
-// rows fit beside the tail's columns (the persistent tail factors them along, §10); the
+// Which evaluations take a tail: plain logpdf, and dense extra rows (posterior, logpdf_multi)
+// when they fit beside the tail's columns (the persistent tail factors them along, §10); the
 // gradient's identity rows (one per column) never do.
+// Dense extra rows (the posterior's cross-covariance rows, the responses of logpdf_multi):
+// every row of every column is nonzero, so both take the same schedule.
+static bool dense_rows(const gaplac_ctx* ctx) { return ctx->xr_mode == 2 || ctx->xr_mode == 3; }
+
 static bool tail_allowed(const gaplac_ctx* ctx) {
-    return ctx->xr_mode == 0 || (ctx->xr_mode == 2 && ctx->tailk && ctx->tail_s > 0 &&
+    return ctx->xr_mode == 0 || (dense_rows(ctx) && ctx->tailk && ctx->tail_s > 0 &&
                                  ctx->xr_tiles + std::min(ctx->tail_s, TAIL_TMAX) <= TAIL_TMAX);
 }
 
@@ -897,8 +915,8 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
     if ((frc = wait_rest(sm, nt))) return frc;  // every split update's rest before the tail
     if (spc[(size_t)nsp] < nt) {
         const int ts = spc[(size_t)nsp], T = nt - ts;
-        // the posterior's cross-covariance rows: factored along inside the tail
-        const int X = ctx->xr_mode == 2 ? ctx->xr_tiles : 0;
+        // dense extra rows: factored along inside the tail
+        const int X = dense_rows(ctx) ? ctx->xr_tiles : 0;
         if (ctx->tailk && T + X <= TAIL_TMAX && (ctx->xr_mode == 0 || X > 0)) {
             // the tail as one persistent dataflow launch
             // the extra rows' super-panel updates of the tail's columns land first
@@ -1025,6 +1043,9 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     if (ctx->xr_mode == 2)
         launch_cross_gram(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->dX, N, ctx->dXs,
                           ctx->xr_M, ctx->dtp);
+    if (ctx->xr_mode == 3)
+        launch_rows_from_matrix(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->xr_Y,
+                                ctx->xr_ldy);
     if (ctx->xr_mode && !ctx->serial) {  // the extra-row stream starts after their init
         HIPQ(ctx, hipEventRecord(ctx->ev_xinit, ctx->s_main));
         HIPQ(ctx, hipStreamWaitEvent(ctx->s_extra, ctx->ev_xinit, 0));
@@ -1034,6 +1055,9 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     if (ctx->xr_mode == 2)
         launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dXs, ctx->xr_M, ctx->dtp, ctx->gpart,
                          ctx->pmean, ctx->pvar);
+    if (ctx->xr_mode == 3)
+        launch_quad_rows(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dres, ctx->gpart, ctx->mres,
+                         ctx->mres ? ctx->mres + ctx->xr_M : nullptr /* (a dry walk has no buffers) */);
     if (ctx->xr_mode == 1) {
         // Fused (single-term groups): alpha = Y z first (HBM-bound, ~0.2 ms alone), then M =
         // -C^{-1} tile by tile contracted in place with every dC/dtheta (cinv_contract_kernel:
@@ -1141,6 +1165,11 @@ int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
                 return set_err(ctx, GAPLAC_E_OOM, "hipMalloc of posterior outputs failed");
             ctx->pmv_elems = M;
         }
+    }
+    if (ctx->xr_mode == 3) {
+        const size_t R = (size_t)ctx->xr_M;
+        if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, R * (size_t)((N + 511) / 512)))) return rc;
+        if ((rc = ensure(ctx, &ctx->mres, &ctx->mres_elems, 2 * R))) return rc;
     }
     if (ctx->xr_mode == 1) {
         const int m = (int)((N + NB - 1) / NB);
@@ -1403,6 +1432,63 @@ int posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64
     if (rc) return rc;
     if (out_mean) HIPCK(ctx, hipMemcpy(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost));
     if (out_var) HIPCK(ctx, hipMemcpy(out_var, ctx->pvar, (size_t)M * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Shared body of gaplac_logpdf_multi / _device: one factorisation, the R responses as
+// dense extra rows (xr_mode 3). Column 0 also rides in row N as v (the evaluation's own
+// quad is not used: all R results come from the extra rows, one code path per column).
+int logpdf_multi_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const double* X, int64_t ldx,
+                      int32_t T, const gaplac_term* terms, double noise, int64_t R, const double* Y, int64_t ldy,
+                      double* out_logpdf, double* out_logdet, double* out_quad) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (R < 0 || !out_logpdf) return set_err(ctx, GAPLAC_E_ARG, "R = %lld < 0 or out_logpdf NULL", (long long)R);
+    auto fill = [&](double lp, double ld, double q) {
+        for (int64_t r = 0; r < R; ++r) {
+            out_logpdf[r] = lp;
+            if (out_quad) out_quad[r] = q;
+        }
+        if (out_logdet && R > 0) *out_logdet = ld;
+    };
+    fill(NAN, NAN, NAN);
+    int rc = check_common(ctx, N, D, X, ldx, noise, ctx /* v: the matrix is checked below */);
+    if (rc) return rc;
+    if (ldy < N || (R > 0 && N > 0 && !Y))
+        return set_err(ctx, GAPLAC_E_ARG, "Y NULL or ldy %lld < N %lld", (long long)ldy, (long long)N);
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (R == 0) return 0;
+    if (N == 0) {  // one empty FiniteGP per column
+        fill(-0.0, 0.0, 0.0);
+        return 0;
+    }
+    if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
+        return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
+    tp.noise = noise;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, N, D, X, ldx, Y, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
+    ctx->xr_Y = Y;
+    ctx->xr_ldy = ldy;
+    if (!on_device) {
+        if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)N * (size_t)R))) return rc;
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)N * 8, Y, (size_t)ldy * 8, (size_t)N * 8, (size_t)R,
+                                    hipMemcpyHostToDevice, ctx->s_main));
+        ctx->xr_Y = ctx->dY;
+        ctx->xr_ldy = N;
+    }
+    ctx->xr_mode = 3;
+    ctx->xr_tiles = (int)((R + NB - 1) / NB);
+    ctx->xr_M = R;
+    EvalResult r;
+    rc = eval_device(ctx, N, D, tp, &r);
+    ctx->xr_mode = 0;
+    ctx->xr_tiles = 0;
+    ctx->xr_Y = nullptr;
+    if (rc) return rc;
+    if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;  // PosDefException: every output stays NaN
+    if (out_logdet) *out_logdet = r.logdet;
+    if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1986,14 +2072,91 @@ int gaplac_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t 
     return 0;
 }
 
+int gaplac_logpdf_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                        const gaplac_term* terms, double noise, int64_t R, const double* Y, int64_t ldy,
+                        double* out_logpdf, double* out_logdet, double* out_quad) {
+    return logpdf_multi_impl(ctx, false, N, D, X, ldx, T, terms, noise, R, Y, ldy, out_logpdf, out_logdet, out_quad);
+}
+
+int gaplac_logpdf_multi_device(gaplac_ctx* ctx, int64_t N, int32_t D, const double* dX, int64_t ldx, int32_t T,
+                               const gaplac_term* terms, double noise, int64_t R, const double* dY, int64_t ldy,
+                               double* out_logpdf, double* out_logdet, double* out_quad) {
+    return logpdf_multi_impl(ctx, true, N, D, dX, ldx, T, terms, noise, R, dY, ldy, out_logpdf, out_logdet, out_quad);
+}
+
+int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                      const gaplac_term* terms, double noise, int64_t R, const double* Z, int64_t ldz, double* out,
+                      int64_t ldo) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (R < 0 || !out || ldz < N || ldo < N || (R > 0 && N > 0 && !Z))
+        return set_err(ctx, GAPLAC_E_ARG, "R < 0, Z / out NULL, or ldz / ldo < N");
+    for (int64_t r = 0; r < R; ++r)  // (rows N .. ldo-1 of out are the caller's)
+        for (int64_t i = 0; i < N; ++i) out[r * ldo + i] = NAN;
+    int rc = check_common(ctx, N, D, X, ldx, noise, ctx /* v: Z is checked above */);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (N == 0 || R == 0) return 0;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, N, D, X, ldx, Z))) return rc;  // column 0 also rides in the v row (unused)
+    const int64_t Np = round_up(N + 1, NB);
+    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Np * (size_t)R))) return rc;
+    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)N * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Np * 8, Z, (size_t)ldz * 8, (size_t)N * 8, (size_t)R,
+                                hipMemcpyHostToDevice, ctx->s_main));
+    tp.noise = noise;
+    EvalResult r;
+    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // diagnostics (GAPLAC_TAIL_TRACE): "N R ms" of the L Z launch alone, appended to <trace path>.lz
+    const bool timed = !ctx->ttrace_path.empty();
+    if (timed) {
+        HIPCK(ctx, hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) {
+            (void)hipEventDestroy(ev[0]);
+            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
+        }
+        (void)hipEventRecord(ev[0], ctx->s_main);
+    }
+    {
+        LaunchGuard g;
+        g.base = ctx->A;
+        g.elems = (int64_t)ctx->A_elems;
+        GuardScope scope(&g);
+        launch_lower_mm(ctx->s_main, ctx->A, Np, N, ctx->dZ, Np, R, ctx->dO, N);
+        if (g.violations) {
+            if (timed) (void)hipEventDestroy(ev[0]), (void)hipEventDestroy(ev[1]);
+            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+        }
+    }
+    if (timed) {
+        float ms = 0.f;
+        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".lz").c_str(), "a") : nullptr) {
+            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)R, (double)ms);
+            std::fclose(f);
+        }
+    }
+    HIPCK(ctx, hipGetLastError());
+    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)N * 8, (size_t)N * 8, (size_t)R,
+                                hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
 // Host-only walk of one evaluation's schedule (no device needed): every launch's element
 // range is checked against the workspace ensure_workspace would allocate for N.
-// mode 0: logpdf; 1: logpdf + gradient (identity rows); 2: posterior at M test points.
+// mode 0: logpdf; 1: logpdf + gradient (identity rows); 2: posterior at M test points;
+// 3: logpdf_multi of M responses (the transposing launch, the rows, the per-row reduction).
 int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* out_launches,
                       int64_t* out_violations, char* msg, int64_t msglen) {
     const bool short_ws = mode >= 8;  // negative control: a workspace one element short
     if (short_ws) mode -= 8;
-    if (N < 1 || mode < 0 || mode > 2 || (mode == 2 && M < 1) || spw < 1 || spw > 8) return GAPLAC_E_ARG;
+    if (N < 1 || mode < 0 || mode > 3 || (mode >= 2 && M < 1) || spw < 1 || spw > 8) return GAPLAC_E_ARG;
     {
         // every tail length the library can launch: the task list is a topological order
         static std::string tail_bad = [] {
@@ -2063,8 +2226,8 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
     gaplac_ctx c;
     c.spw = spw;
     c.xr_mode = mode;
-    c.xr_tiles = mode == 1 ? (int)(round_up(N + 1, NB) / NB) : mode == 2 ? (int)((M + NB - 1) / NB) : 0;
-    c.xr_M = mode == 2 ? M : 0;
+    c.xr_tiles = mode == 1 ? (int)(round_up(N + 1, NB) / NB) : mode >= 2 ? (int)((M + NB - 1) / NB) : 0;
+    c.xr_M = mode >= 2 ? M : 0;
     LaunchGuard g;
     const int rc = dry_walk(c, N, g, short_ws ? 1 : 0);
     if (out_launches) *out_launches = g.launches;

@@ -313,6 +313,19 @@ void launch_posterior(hipStream_t s, const double* A, int64_t lda, int64_t Np, i
 // ---- rand(FiniteGP): out = L z over the factor's lower triangle (partial: ceil(N/512) * N) ----
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,
                      double* out);
+// ---- matrix forms: many vectors per factorisation ----
+// Extra rows Np .. Np + 128 mt - 1 = Y^T (Y is N x R, leading dimension ldy): mt x nt tiles,
+// zero outside response r < R and observation i < N.
+void launch_rows_from_matrix(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t R, int mt,
+                             const double* Y, int64_t ldy);
+// After the factorisation and launch_reduce (same stream): quad_r = sum_k W^T[r,k]^2 and
+// logpdf_r = -(N log 2pi + res->logdet + quad_r) / 2 (partial: ceil(N/512) * R doubles).
+void launch_quad_rows(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t R,
+                      const EvalResult* res, double* partial, double* quad, double* logpdf);
+// out = tril(L) Z over the factor in A (fp64 MFMA): Z is N x R with an even leading dimension
+// ldz >= roundup(N, 32) and 16-byte aligned (rows >= N are read and masked), out N x R (ldo).
+void launch_lower_mm(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* Z, int64_t ldz, int64_t R,
+                     double* out, int64_t ldo);
 // The same tiles of M = -C^{-1} contracted in place (never stored) with every dC/dtheta:
 // partial as launch_grad_contract's; alpha must be final before the launch; formulas whose
 // groups are all single terms only.

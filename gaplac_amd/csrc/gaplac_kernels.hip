@@ -2382,6 +2382,179 @@ __global__ __launch_bounds__(256) void lower_mv_reduce_kernel(const double* __re
     out[i] = a;
 }
 
+// ---------------------------------------------------------------------------------
+// Matrix forms (AbstractGPs logpdf(fx, Y::AbstractMatrix) and
+// rand(rng, fx, n)): many vectors per factorisation.
+//   logpdf: the rows below the matrix hold Y^T (one row per response); factoring them along
+//           leaves W^T = Y^T L^{-T} there, so quad_r = sum_k W^T[r,k]^2.
+//   rand:   OUT = tril(L) Z on the fp64 MFMA.
+// ---------------------------------------------------------------------------------
+
+// Response rows: tile (E, J) of the extra rows = Y^T, A[i lda + Np + r] = Y[i + r ldy], 0
+// outside r < R, i < N. Reads run along i, writes along r: each 128 x 128 tile goes through
+// LDS in four strips of 32 columns of A (row stride NB + 1: both sides conflict-free).
+__global__ __launch_bounds__(256) void rows_from_matrix_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                               int64_t N, int64_t R, const double* __restrict__ Y,
+                                                               int64_t ldy) {
+    __shared__ double t[32][NB + 1];
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * NB, r0 = (int64_t)blockIdx.y * NB;
+    for (int s = 0; s < NB / 32; ++s) {
+        {
+            const int ii = tid & 31, rq = tid >> 5;
+            const int64_t i = i0 + 32 * s + ii;
+#pragma unroll 4
+            for (int it = 0; it < NB / 8; ++it) {
+                const int rr = rq + 8 * it;
+                const int64_t r = r0 + rr;
+                t[ii][rr] = (i < N && r < R) ? Y[i + r * ldy] : 0.0;
+            }
+        }
+        __syncthreads();
+        {
+            const int rr = tid & (NB - 1), iq = tid >> 7;
+            double* dst = A + (i0 + 32 * s) * lda + Np + r0 + rr;
+#pragma unroll 4
+            for (int it = 0; it < 16; ++it) {
+                const int ii = iq + 2 * it;
+                dst[(int64_t)ii * lda] = t[ii][rr];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Partial sums over 512-column chunks of the response rows: pq = |W^T|^2 (the variance half
+// of post_partial_kernel).
+__global__ __launch_bounds__(256) void quad_partial_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                           int64_t N, int64_t R, double* __restrict__ pq) {
+    const int64_t k0 = (int64_t)blockIdx.y * 512;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= R) return;
+    const double* y = A + k0 * lda + Np + j;
+    const int kn = (int)((N - k0) < 512 ? (N - k0) : 512);
+    double v0 = 0.0, v1 = 0.0;
+    int kk = 0;
+    for (; kk + 2 <= kn; kk += 2) {
+        const double a = y[(int64_t)kk * lda], b = y[(int64_t)(kk + 1) * lda];
+        v0 += a * a;
+        v1 += b * b;
+    }
+    for (; kk < kn; ++kk) {
+        const double a = y[(int64_t)kk * lda];
+        v0 += a * a;
+    }
+    pq[(int64_t)blockIdx.y * R + j] = v0 + v1;
+}
+
+// quad_r = sum of the partials (fixed order), logpdf_r as reduce_final_kernel writes the
+// single one, from the logdet that kernel left in res (same stream, launched before).
+__global__ __launch_bounds__(256) void quad_finish_kernel(const double* __restrict__ pq, int64_t R, int nk, int64_t N,
+                                                          const EvalResult* __restrict__ res,
+                                                          double* __restrict__ quad, double* __restrict__ logpdf) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= R) return;
+    double q = 0.0;
+    for (int y = 0; y < nk; ++y) q += pq[(int64_t)y * R + j];
+    const double log2pi = 1.8378770664093453;  // Julia's log2π
+    double lp = -(((double)N * log2pi + res->logdet) + q) / 2.0;
+    if (res->info != ~0ull) lp = __builtin_nan("");
+    quad[j] = q;
+    logpdf[j] = lp;
+}
+
+// OUT = tril(L) Z. One workgroup: a 128-row tile I of OUT x LM_CB columns, walking the
+// factor's columns k < (I + 1) NB in chunks of LM_KC; wave w owns rows 32 w .. 32 w + 31 (two
+// 16-row fragments) x the 64 columns (four fragments). MFMA operands (D = A B, D row from A):
+// A = Z^T (fragment row = column of Z), B = L^T (fragment column = row of L), so a lane's four
+// results are OUT[i = .. + (lane & 15)][c = .. + (lane >> 4) + 4 rg]: stores run along i.
+// The chunk is staged through registers (the next chunk's loads fly during this chunk's
+// MFMAs) so that it can be masked on the way: L[i,k] = 0 for k > i (the diagonal tiles' upper
+// parts hold junk), for i >= N and k >= N (row N holds the v row), Z = 0 for k >= N, c >= R.
+// Each output element is one accumulator chain in ascending k: a column's result does not
+// depend on R or on where the column stands.
+constexpr int LM_CB = 64;
+constexpr int LM_KC = 32;
+constexpr int LM_LS = NB + 16;     // L chunk row stride (as LR)
+constexpr int LM_ZS = LM_KC + 2;   // Z chunk row stride: 16 rows x 2 k land on 32 distinct 8-byte banks
+__global__ __launch_bounds__(256, 2) void lower_mm_kernel(const double* __restrict__ A, int64_t lda, int64_t N,
+                                                          const double* __restrict__ Z, int64_t ldz, int64_t R,
+                                                          double* __restrict__ O, int64_t ldo, int ncb) {
+    __shared__ __attribute__((aligned(16))) double Ls[LM_KC][LM_LS];
+    __shared__ __attribute__((aligned(16))) double Zs[LM_CB][LM_ZS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int fr = lane >> 4, fc = lane & 15;
+    const int b = (int)blockIdx.x;
+    const int I = (int)gridDim.x / ncb - 1 - b / ncb;  // heavy row tiles first
+    const int64_t i0 = (int64_t)I * NB, c0 = (int64_t)(b % ncb) * LM_CB;
+    const int64_t kend = (i0 + NB) < N ? (i0 + NB) : N;
+    const int nch = (int)((kend + LM_KC - 1) / LM_KC);
+    const int li = 2 * (tid & 63), lk = tid >> 6;  // L: rows li, li + 1 of chunk columns lk + 4 it
+    const int zr = tid >> 2, zk = (tid & 3) * 8;   // Z: column zr, chunk rows zk .. zk + 7
+    double2 lreg[LM_KC / 4], zreg[4];
+    auto fetch = [&](int ch) {
+        const int64_t k0 = (int64_t)ch * LM_KC;
+        const int64_t i = i0 + li;
+#pragma unroll
+        for (int it = 0; it < LM_KC / 4; ++it) {
+            const int64_t k = k0 + lk + 4 * it;
+            double2 v = *reinterpret_cast<const double2*>(A + k * lda + i);
+            v.x = (k <= i && i < N) ? v.x : 0.0;
+            v.y = (k <= i + 1 && i + 1 < N) ? v.y : 0.0;
+            lreg[it] = v;
+        }
+        const int64_t c = c0 + zr;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t k = k0 + zk + 2 * q;
+            double2 v = make_double2(0.0, 0.0);
+            if (c < R) v = *reinterpret_cast<const double2*>(Z + c * ldz + k);
+            v.x = k < N ? v.x : 0.0;
+            v.y = k + 1 < N ? v.y : 0.0;
+            zreg[q] = v;
+        }
+    };
+    d4 acc[2][4];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj) acc[ni][mj] = d4{0.0, 0.0, 0.0, 0.0};
+    fetch(0);
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();  // every wave is done with the previous chunk
+#pragma unroll
+        for (int it = 0; it < LM_KC / 4; ++it) *reinterpret_cast<double2*>(&Ls[lk + 4 * it][li]) = lreg[it];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *reinterpret_cast<double2*>(&Zs[zr][zk + 2 * q]) = zreg[q];
+        __syncthreads();
+        if (ch + 1 < nch) fetch(ch + 1);
+#pragma unroll
+        for (int ks = 0; ks < LM_KC; ks += 4) {
+            double fa[4], fb[2];
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb[ni] = Ls[ks + fr][32 * w + 16 * ni + fc];
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj) fa[mj] = Zs[16 * mj + fc][ks + fr];
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+                    acc[ni][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mj], fb[ni], acc[ni][mj], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        const int64_t i = i0 + 32 * w + 16 * ni + fc;
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int64_t c = c0 + 16 * mj + fr + 4 * rg;
+                if (i < N && c < R) O[c * ldo + i] = acc[ni][mj][rg];
+            }
+    }
+}
+
 // =================================================================================
 // Persistent tail: the last T <= TAIL_TMAX tile columns ts .. nt-1
 // of the factorisation in ONE launch, as a dataflow of tile tasks instead of per-column
@@ -3655,6 +3828,32 @@ void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, con
     lower_mv_partial_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)nk), dim3(256), 0, s>>>(A, lda, N, z,
                                                                                                 partial);
     lower_mv_reduce_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(partial, N, nk, out);
+}
+
+void launch_rows_from_matrix(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t R, int mt,
+                             const double* Y, int64_t ldy) {
+    if (nt <= 0 || mt <= 0) return;
+    if (!guard_launch("rows_from_matrix_kernel", A, 0, ((int64_t)nt * NB - 1) * lda + Np + (int64_t)mt * NB)) return;
+    rows_from_matrix_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, R, Y, ldy);
+}
+
+void launch_quad_rows(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t R,
+                      const EvalResult* res, double* partial, double* quad, double* logpdf) {
+    if (R <= 0) return;
+    if (!guard_launch("quad_partial_kernel", A, 0, (N - 1) * lda + Np + R)) return;
+    const int nk = (int)((N + 511) / 512);
+    quad_partial_kernel<<<dim3((unsigned)((R + 255) / 256), (unsigned)nk), dim3(256), 0, s>>>(A, lda, Np, N, R,
+                                                                                            partial);
+    quad_finish_kernel<<<dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s>>>(partial, R, nk, N, res, quad, logpdf);
+}
+
+void launch_lower_mm(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* Z, int64_t ldz, int64_t R,
+                     double* out, int64_t ldo) {
+    if (N <= 0 || R <= 0) return;
+    const int64_t ni = (N + NB - 1) / NB, ncb = (R + LM_CB - 1) / LM_CB;
+    // the last row tile's chunks end at column roundup(N, LM_KC) <= ni NB, rows at ni NB
+    if (!guard_launch("lower_mm_kernel", A, 0, (ni * NB - 1) * lda + ni * NB)) return;
+    lower_mm_kernel<<<dim3((unsigned)(ni * ncb)), dim3(256), 0, s>>>(A, lda, N, Z, ldz, R, out, ldo, (int)ncb);
 }
 
 void launch_tail(hipStream_t s, const TailArgs& a, int grid, KTime* kt) {

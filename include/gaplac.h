@@ -165,6 +165,42 @@ int gaplac_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
 int gaplac_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
                 int32_t T, const gaplac_term* terms, double noise, const double* z, double* out);
 
+/* Matrix form of logpdf: R response vectors (the columns of Y, N x R column-major, leading
+ * dimension ldy) scored against one FiniteGP with ONE factorisation: the responses ride along
+ * as R extra rows of the factored matrix (as the posterior's test points do), so about a
+ * thousand of them cost a few ms beyond a single gaplac_logpdf at N = 16384.
+ *     out_logpdf[r] = -( N*log(2*pi) + logdet + ||U^-T Y[:,r]||^2 ) / 2,  out_quad[r] the last term
+ * out_logdet (one value) and out_quad (R values) may be NULL. Same return convention as
+ * gaplac_logpdf; on a PosDefException (info > 0) every output entry is NaN. GAPLAC_E_ARG also
+ * for R < 0, Y NULL with R > 0 and N > 0, ldy < N, out_logpdf NULL. R = 0: returns 0 after the
+ * argument and term checks and writes nothing; N = 0: -0.0 per column. All R rows must fit in
+ * device memory beside the matrix (GAPLAC_E_OOM otherwise, as for the posterior's M; no chunking).
+ * Replaces: AbstractGPs.logpdf(f::FiniteGP, Y::AbstractMatrix) (AbstractGPs 0.5.12: one
+ *           mean_and_cov + cholesky, then diag_Xt_invA_X(C, Y)), one log-density per column. */
+int gaplac_logpdf_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                        int32_t T, const gaplac_term* terms, double noise,
+                        int64_t R, const double* Y, int64_t ldy,
+                        double* out_logpdf, double* out_logdet, double* out_quad);
+/* Same, with X and Y already resident in device memory (HBM) on the ctx's device; Y is read
+ * in place (not copied). Outputs are host pointers.
+ * Replaces: the same logpdf(f::FiniteGP, Y::AbstractMatrix) for device-resident inputs. */
+int gaplac_logpdf_multi_device(gaplac_ctx* ctx, int64_t N, int32_t D, const double* dX, int64_t ldx,
+                               int32_t T, const gaplac_term* terms, double noise,
+                               int64_t R, const double* dY, int64_t ldy,
+                               double* out_logpdf, double* out_logdet, double* out_quad);
+
+/* Matrix form of rand: R draws with one factorisation, out = L Z with Z the N x R matrix of
+ * standard-normal values the caller drew (leading dimension ldz) and out N x R (leading
+ * dimension ldo; rows N .. ldo-1 are never written). A column's sample does not depend on
+ * R or on the column's position. Same return convention as gaplac_rand (out NaN on failure).
+ * GAPLAC_E_ARG also for R < 0, Z NULL with R > 0 and N > 0, ldz < N, ldo < N, out NULL;
+ * R = 0 or N = 0: returns 0 after the checks, out untouched.
+ * Replaces: rand(rng, f::FiniteGP, n::Int) = cholesky(C).U' * randn(rng, N, n) (zero mean) of
+ *           AbstractGPs 0.5.12; CLI/src/sample.jl:25's one draw is vec(rand(rng, f, 1)). */
+int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                      int32_t T, const gaplac_term* terms, double noise,
+                      int64_t R, const double* Z, int64_t ldz, double* out, int64_t ldo);
+
 /* Debug / parity entries (tests only; not on the timed path). */
 /* Gram matrix sum_t K_t(X) + noise*I as a dense N×N column-major host matrix
  * (replaces KernelFunctions.kernelmatrix + Diagonal(Fill(noise, N))). */
@@ -229,7 +265,8 @@ int gaplac_reset_stats(gaplac_ctx* ctx);
 
 /* Launch-footprint check of one evaluation's schedule, on the host only (no device, no
  * context): walks every launch gaplac_logpdf (mode 0), gaplac_logpdf_grad (mode 1) or
- * gaplac_posterior_mean_var at M test points (mode 2) would enqueue for order N with
+ * gaplac_posterior_mean_var at M test points (mode 2) or gaplac_logpdf_multi of M responses
+ * (mode 3) would enqueue for order N with
  * super-panel width spw, and checks the element range each launch's grid touches against
  * the workspace the context allocates for N. Every launcher applies the same check before
  * a real launch (a violating launch is not enqueued; the entry returns GAPLAC_E_ARG).

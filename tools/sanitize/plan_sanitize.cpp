@@ -35,12 +35,12 @@ int main() {
         sizes.push_back(n);
     long checks = 0;
     for (int spw : {1, 2, 4, 5, 8})
-        for (int mode : {0, 1, 2})
+        for (int mode : {0, 1, 2, 3})  // 3: logpdf_multi, M responses as dense extra rows
             for (int64_t M : {1, 130, 1000, 6016, 6200}) {
-                if (mode != 2 && M != 1) continue;
+                if (mode < 2 && M != 1) continue;
                 for (int64_t N : sizes) {
                     if (mode == 1 && N > 16384) continue;
-                    const int rc = gaplac_plan_check(N, mode, mode == 2 ? M : 0, spw, &a, &b, msg, sizeof msg);
+                    const int rc = gaplac_plan_check(N, mode, mode >= 2 ? M : 0, spw, &a, &b, msg, sizeof msg);
                     EXPECT(rc == 0 && b == 0, "plan_check N=%lld mode=%d M=%lld spw=%d: rc %d violations %lld %s",
                            (long long)N, mode, (long long)M, spw, rc, (long long)b, msg);
                     ++checks;
@@ -50,6 +50,10 @@ int main() {
     for (int64_t N : {1, 127, 255, 300, 4096}) {
         const int rc = gaplac_plan_check(N, 8, 0, 4, &a, &b, msg, sizeof msg);
         EXPECT(rc == 0 && b >= 1, "negative control N=%lld not reported", (long long)N);
+    }
+    for (int64_t N : {1, 128, 300, 4096}) {  // mode 11: logpdf_multi against the short workspace
+        const int rc = gaplac_plan_check(N, 11, 64, 4, &a, &b, msg, sizeof msg);
+        EXPECT(rc == 0 && b >= 1, "negative control (mode 11) N=%lld not reported", (long long)N);
     }
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
