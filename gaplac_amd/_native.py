@@ -35,6 +35,9 @@ EXPORTED = (
     "gaplac_logpdf_multi",
     "gaplac_logpdf_multi_device",
     "gaplac_rand_multi",
+    "gaplac_posterior_mean_cov",
+    "gaplac_posterior_rand",
+    "gaplac_posterior_logpdf",
     "gaplac_gram",
     "gaplac_gram_time",
     "gaplac_factor",
@@ -43,6 +46,7 @@ EXPORTED = (
     "gaplac_reset_stats",
     "gaplac_plan_check",
     "gaplac_plan_check_schedule",
+    "gaplac_plan_check_joint",
     "gaplac_dist_create",
     "gaplac_dist_destroy",
     "gaplac_dist_last_error",
@@ -157,6 +161,11 @@ def load() -> ctypes.CDLL:
     lib.gaplac_logpdf_multi.argtypes = multi + [c_void_p, _DP, c_void_p]
     lib.gaplac_logpdf_multi_device.argtypes = multi + [c_void_p, _DP, c_void_p]
     lib.gaplac_rand_multi.argtypes = multi + [c_void_p, c_int64]
+    # (the joint posterior entries: the head of posterior_mean_var, then noise_s)
+    joint = common + [c_int64, c_void_p, c_int64, c_double]
+    lib.gaplac_posterior_mean_cov.argtypes = joint + [c_void_p, c_void_p, c_int64]
+    lib.gaplac_posterior_rand.argtypes = joint + [c_int64, c_void_p, c_int64, c_void_p, c_int64]
+    lib.gaplac_posterior_logpdf.argtypes = joint + [c_int64, c_void_p, c_int64, c_void_p, _DP, c_void_p]
     lib.gaplac_gram.argtypes = [
         c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Term), c_double, c_void_p, c_int64,
     ]
@@ -171,6 +180,7 @@ def load() -> ctypes.CDLL:
     _I32P, _I64P, _VPP = POINTER(c_int32), POINTER(c_int64), POINTER(c_void_p)
     lib.gaplac_plan_check.argtypes = [c_int64, c_int32, c_int64, c_int32, _I64P, _I64P, c_char_p, c_int64]
     lib.gaplac_plan_check_schedule.argtypes = [c_int64, c_int32, c_int32, c_int32, c_int32, _I64P, c_char_p, c_int64]
+    lib.gaplac_plan_check_joint.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, _I64P, _I64P, c_char_p, c_int64]
     lib.gaplac_dist_create.argtypes = [c_int, c_int, c_int, c_int, _VPP]
     lib.gaplac_dist_destroy.argtypes = [c_void_p]
     lib.gaplac_dist_last_error.argtypes = [c_void_p]

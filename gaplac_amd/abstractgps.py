@@ -75,6 +75,16 @@ def logpdf(fx: FiniteGP, y, ctx: backend.Context | None = None, full: bool = Fal
     A matrix y (N x R) is AbstractGPs' logpdf(fx, Y::AbstractMatrix): one log-density per
     column, shape (R,), from one factorisation (gaplac_logpdf_multi)."""
     _gate()
+    if isinstance(fx, FinitePosteriorGP):
+        # logpdf(posterior(fx, y)(xs, noise), ys): a vector gives a scalar, a matrix one value
+        # per column (gaplac_posterior_logpdf)
+        ys = np.asarray(y, dtype=np.float64)
+        if ys.ndim == 0 or ys.ndim > 2 or ys.shape[0] != len(fx):
+            raise F.ArgumentError("DimensionMismatch: length of ys does not match the test points")
+        res = fx._logpdf(ys if ys.ndim == 2 else ys[:, None], ctx, full)
+        if ys.ndim == 2:
+            return res
+        return (res[0][0], res[1], res[2][0]) if full else res[0]
     ctx = ctx or backend.default_context()
     y = np.asarray(y, dtype=np.float64)
     if y.ndim == 0 or y.shape[0] != len(fx):
@@ -128,6 +138,41 @@ class PosteriorGP:
     def var(self, x):
         return self.mean_and_var(x)[1]
 
+    def __call__(self, x, noise=0.0):
+        """AbstractGPs' fp(xs, σ²): the posterior at the rows of x, jointly, with observation
+        variance noise there (a FiniteGP{<:PosteriorGP})."""
+        return FinitePosteriorGP(self, x, noise)
+
+
+class FinitePosteriorGP:
+    """posterior(fx, y)(xs, noise): a finite-dimensional Gaussian with mean m and covariance
+    Σ* (gaplac.h, the joint posterior entries). Every query is one library call."""
+
+    def __init__(self, f: PosteriorGP, x, noise=0.0):
+        self.f = f
+        self.x = np.asfortranarray(f._xs(x))
+        self.noise = float(noise)
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    def _args(self):
+        pr = self.f.prior
+        return pr.x, pr.terms, pr.noise, self.f.y, self.x, self.noise
+
+    def _ctx(self, ctx):
+        return ctx or self.f.ctx or backend.default_context()
+
+    def mean_and_cov(self, ctx=None):
+        _gate()
+        return self._ctx(ctx).posterior_mean_cov(*self._args())
+
+    def _rand(self, z, ctx):
+        return self._ctx(ctx).posterior_rand(*self._args(), z)
+
+    def _logpdf(self, ys, ctx, full):
+        return self._ctx(ctx).posterior_logpdf(*self._args(), ys, full=full)
+
 
 def posterior(fx: FiniteGP, y, ctx: backend.Context | None = None) -> PosteriorGP:
     """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8)."""
@@ -139,6 +184,17 @@ def mean_and_var(f: PosteriorGP, x):
     return f.mean_and_var(x)
 
 
+def mean_and_cov(fpx: FinitePosteriorGP, ctx: backend.Context | None = None):
+    """AbstractGPs.mean_and_cov(posterior(fx, y)(xs, noise)): the mean and the full M x M
+    covariance at the test points (gaplac_posterior_mean_cov)."""
+    return fpx.mean_and_cov(ctx)
+
+
+def cov(fpx: FinitePosteriorGP, ctx: backend.Context | None = None):
+    """AbstractGPs.cov(posterior(fx, y)(xs, noise))."""
+    return fpx.mean_and_cov(ctx)[1]
+
+
 def rand(fx: FiniteGP, n=None, z=None, rng=None, ctx: backend.Context | None = None):
     """rand(rng, fx) = cholesky(C).U' * randn(rng, N) for the zero-mean FiniteGP
     (CLI/src/sample.jl:25). The standard-normal draws stay on the host: pass z, or an rng
@@ -147,12 +203,19 @@ def rand(fx: FiniteGP, n=None, z=None, rng=None, ctx: backend.Context | None = N
     an N x n matrix from one factorisation (gaplac_rand_multi), the draws made as
     rng.standard_normal((N, n))."""
     _gate()
-    ctx = ctx or backend.default_context()
     if n is not None and z is not None and (np.ndim(z) != 2 or np.shape(z)[1] != int(n)):
         raise F.ArgumentError("DimensionMismatch: z must be N x n when both n and z are given")
     if z is None:
         rng = rng if rng is not None else np.random.default_rng()
         z = rng.standard_normal(len(fx) if n is None else (len(fx), int(n)))
+    if isinstance(fx, FinitePosteriorGP):
+        # rand(rng, posterior(fx, y)(xs, noise)[, n]) = m + L* z (gaplac_posterior_rand)
+        z = np.asarray(z, dtype=np.float64)
+        if z.ndim == 0 or z.ndim > 2 or z.shape[0] != len(fx):
+            raise F.ArgumentError("DimensionMismatch: z does not match the test points")
+        out = fx._rand(z if z.ndim == 2 else z[:, None], ctx)
+        return out if z.ndim == 2 else out[:, 0]
+    ctx = ctx or backend.default_context()
     if np.ndim(z) == 2:
         return ctx.rand_multi(fx.x, fx.terms, fx.noise, z)
     return ctx.rand(fx.x, fx.terms, fx.noise, z)

@@ -279,6 +279,72 @@ class Context:
         self._check(rc)
         return out
 
+    def _joint_head(self, X, terms, noise, y, Xs, noise_s):
+        """The argument head the three joint posterior entries share (after self.h)."""
+        Xc = _colmajor(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, D = Xc.shape
+        if y.ndim != 1 or y.shape[0] != N:
+            raise ArgumentError(f"length of y ({y.shape[0] if y.ndim else 0}) != N ({N})")
+        Xsc = _colmajor(Xs)
+        M = Xsc.shape[0]
+        if Xsc.shape[1] != D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {D}")
+        terms = list(terms)
+        ta = term_array(terms)
+        head = (N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+                y.ctypes.data_as(c_void_p), M, Xsc.ctypes.data_as(c_void_p), max(M, 1), float(noise_s))
+        return head, (Xc, y, Xsc, ta), M
+
+    def posterior_mean_cov(self, X, terms, noise: float, y, Xs, noise_s: float = 0.0):
+        """(mean, cov) of the posterior of the zero-mean FiniteGP given y, jointly at the rows of
+        Xs with observation variance noise_s there (gaplac_posterior_mean_cov): cov is the full
+        symmetric M x M matrix."""
+        head, keep, M = self._joint_head(X, terms, noise, y, Xs, noise_s)
+        mean = np.empty(M, dtype=np.float64)
+        cov = np.empty((M, M), dtype=np.float64, order="F")
+        mb = mean if M else np.empty(1)  # (an empty result still passes valid pointers)
+        cb = cov if M else np.empty(1)
+        rc = self.lib.gaplac_posterior_mean_cov(self.h, *head, mb.ctypes.data_as(c_void_p),
+                                                cb.ctypes.data_as(c_void_p), max(M, 1))
+        self._check(rc)
+        return mean, cov
+
+    def posterior_rand(self, X, terms, noise: float, y, Xs, noise_s: float, Z):
+        """m 1^T + L* Z (gaplac_posterior_rand): one joint posterior draw at the rows of Xs per
+        column of the standard-normal matrix Z (M x R). Returns M x R (column-major)."""
+        head, keep, M = self._joint_head(X, terms, noise, y, Xs, noise_s)
+        Zc = np.asarray(Z, dtype=np.float64)
+        if Zc.ndim != 2:
+            raise ArgumentError(f"Z must be a matrix (M x R), got {Zc.ndim} dimension(s)")
+        Zc = np.asfortranarray(Zc)
+        if Zc.shape[0] != M:
+            raise ArgumentError(f"rows of Z ({Zc.shape[0]}) != M ({M})")
+        R = Zc.shape[1]
+        out = np.empty((M, R), dtype=np.float64, order="F")
+        buf = out if out.size else np.empty(1)
+        rc = self.lib.gaplac_posterior_rand(self.h, *head, R, Zc.ctypes.data_as(c_void_p), max(M, 1),
+                                            buf.ctypes.data_as(c_void_p), max(M, 1))
+        self._check(rc)
+        return out
+
+    def posterior_logpdf(self, X, terms, noise: float, y, Xs, noise_s: float, Ys, full: bool = False):
+        """logpdf of every column of Ys (M x R) under the joint posterior at the rows of Xs
+        (gaplac_posterior_logpdf): an array of R, or (logpdf[R], logdet, quad[R]) with full=True."""
+        head, keep, M = self._joint_head(X, terms, noise, y, Xs, noise_s)
+        Yc = np.asarray(Ys, dtype=np.float64)
+        if Yc.ndim != 2:
+            raise ArgumentError(f"Ys must be a matrix (M x R), got {Yc.ndim} dimension(s)")
+        Yc = np.asfortranarray(Yc)
+        if Yc.shape[0] != M:
+            raise ArgumentError(f"rows of Ys ({Yc.shape[0]}) != M ({M})")
+        R = Yc.shape[1]
+        lp, ld, q = self._multi_outputs(R)
+        rc = self.lib.gaplac_posterior_logpdf(self.h, *head, R, Yc.ctypes.data_as(c_void_p), max(M, 1),
+                                              lp.ctypes.data_as(c_void_p), byref(ld), q.ctypes.data_as(c_void_p))
+        self._check(rc)
+        return (lp[:R], ld.value, q[:R]) if full else lp[:R]
+
     def gram(self, X, terms, noise: float = 0.0) -> np.ndarray:
         Xc = _colmajor(X)
         N, D = Xc.shape

@@ -174,6 +174,13 @@ struct gaplac_ctx {
     double* pmean = nullptr;
     double* pvar = nullptr;
     size_t pmv_elems = 0;
+    // Joint posterior: the order-M workspace that post_cov_kernel fills and the
+    // second factorisation runs in. For that factorisation A and B change places and preloaded
+    // is set: the evaluation finds its matrix already built (no Gram launch).
+    double* B = nullptr;
+    size_t B_elems = 0;
+    bool preloaded = false;
+    const double* xr_sub = nullptr;  // mode 3: N values subtracted from every response (or nullptr)
     // gradient: alpha, partial sums, the XCD-balanced C^{-1} tile list
     double* galpha = nullptr;
     size_t galpha_elems = 0;
@@ -255,7 +262,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        buf(&c->pmean), buf(&c->pvar), buf(&c->galpha), buf(&c->gdv), buf(&c->gz), buf(&c->gpart),
                        buf(&c->gout, gout_bytes), buf(&c->hgout, gout_bytes, true), buf(&c->dgp, sizeof(GradTermPack)),
                        buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist), large(&c->dY, &c->dY_elems),
-                       buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems)};
+                       buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems),
+                       large(&c->B, &c->B_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -584,7 +592,7 @@ static bool whole_in_tail(const gaplac_ctx* ctx, int nt) {
 #define GAPLAC_TAIL_GRAM 1
 #endif
 static bool gram_in_tail(const gaplac_ctx* ctx, int nt, int64_t lda) {
-    return GAPLAC_TAIL_GRAM && ctx->xr_mode == 0 && whole_in_tail(ctx, nt) &&
+    return GAPLAC_TAIL_GRAM && ctx->xr_mode == 0 && !ctx->preloaded && whole_in_tail(ctx, nt) &&
            ((int64_t)(NB - 1) * lda + NB) * 8 < ((int64_t)1 << 31);
 }
 
@@ -1032,7 +1040,12 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     const double bpt = 8.0 * NB * NB;  // bytes per tile
     const double b1 = bpt * (tri(nt) - tri(std::max(0, nt - ctx->spw))) + 8.0 * (double)N * (D + 1);
     const double b2 = bpt * tri(std::max(0, nt - ctx->spw));
-    if (!gram_tail) {  // (else the tail's first tasks build it)
+    if (ctx->preloaded) {
+        // the matrix is already in the workspace (post_cov_kernel, earlier on s_main): the panel
+        // stream's two waits for the Gram hold behind it
+        HIPQ(ctx, hipEventRecord(ctx->ev_gram, ctx->s_main));
+        HIPQ(ctx, hipEventRecord(ctx->ev_gram2, ctx->s_main));
+    } else if (!gram_tail) {  // (else the tail's first tasks build it)
         launch_gram(ctx->s_main, ctx->A, lda, N, nt, ctx->dX, N, ctx->dv, ctx->dtp, 1, ctx->spw, slot(ctx, 1, b1));
         HIPQ(ctx, hipEventRecord(ctx->ev_gram, ctx->s_main));
         launch_gram_queue(ctx->s_main, ctx->A, lda, N, nt, ctx->dX, N, ctx->dv, ctx->dtp, ctx->spw, nt, 2, ctx->dres,
@@ -1045,7 +1058,7 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
                           ctx->xr_M, ctx->dtp);
     if (ctx->xr_mode == 3)
         launch_rows_from_matrix(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->xr_Y,
-                                ctx->xr_ldy);
+                                ctx->xr_ldy, ctx->xr_sub);
     if (ctx->xr_mode && !ctx->serial) {  // the extra-row stream starts after their init
         HIPQ(ctx, hipEventRecord(ctx->ev_xinit, ctx->s_main));
         HIPQ(ctx, hipStreamWaitEvent(ctx->s_extra, ctx->ev_xinit, 0));
@@ -1487,6 +1500,248 @@ int logpdf_multi_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, con
     if (rc) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;  // PosDefException: every output stays NaN
     if (out_logdet) *out_logdet = r.logdet;
+    if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- joint posterior at test points ----
+// Argument checks the three entries share, after their own (sizes and output pointers).
+int joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise, const double* y,
+                int64_t M, const double* Xs, int64_t ldxs, double noise_s) {
+    int rc = check_common(ctx, N, D, X, ldx, noise, y);
+    if (rc) return rc;
+    if (M > 0 && D > 0 && (!Xs || ldxs < M)) return set_err(ctx, GAPLAC_E_ARG, "Xs NULL or ldxs < M");
+    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
+        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
+    return 0;
+}
+
+// The second factorisation runs in B: A and B change places for as long as this lives.
+struct WsSwap {
+    gaplac_ctx* c;
+    explicit WsSwap(gaplac_ctx* ctx) : c(ctx) { flip(true); }
+    ~WsSwap() {
+        flip(false);
+        c->xr_mode = 0;
+        c->xr_tiles = 0;
+        c->xr_Y = nullptr;
+        c->xr_sub = nullptr;
+    }
+    void flip(bool on) {
+        std::swap(c->A, c->B);
+        std::swap(c->A_elems, c->B_elems);
+        c->preloaded = on;
+    }
+};
+
+// Stages 1 and 2: the posterior evaluation (xr_mode 2: V^T below the factor, the mean in
+// ctx->pmean), then, with want_cov, post_cov_kernel writes the augmented matrix of Sigma* into
+// ctx->B, laid out for a factorisation of order M with rows_tiles extra tile rows. tp comes in
+// with the training noise and leaves with noise_s (the pack of stages 2 and 3, also in ctx->dtp).
+int joint_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, TermPack& tp, const double* y,
+                 int64_t M, const double* Xs, int64_t ldxs, double noise_s, int rows_tiles, bool want_cov) {
+    int rc;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
+    const size_t nxs = (size_t)M * (size_t)(D > 0 ? D : 1);
+    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, nxs))) return rc;
+    if (D > 0)
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)M * 8, Xs, (size_t)ldxs * 8, (size_t)M * 8, (size_t)D,
+                                    hipMemcpyHostToDevice, ctx->s_main));
+    const int mt = (int)((M + NB - 1) / NB);
+    ctx->xr_mode = 2;
+    ctx->xr_tiles = mt;
+    ctx->xr_M = M;
+    EvalResult r;
+    rc = eval_device(ctx, N, D, tp, &r);
+    ctx->xr_mode = 0;
+    ctx->xr_tiles = 0;
+    if (rc) return rc;
+    if ((rc = finish(r, nullptr, nullptr, nullptr)))
+        return set_err(ctx, rc, "the training covariance K(X) + noise I is not positive definite (leading minor %d)", rc);
+    if (!want_cov) return 0;
+    const int64_t Np = round_up(N + 1, NB), lda = Np + (int64_t)NB * mt;
+    const int64_t Mp = round_up(M + 1, NB), ldb = Mp + (int64_t)NB * rows_tiles;
+    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)ldb * (size_t)Mp))) return rc;
+    tp.noise = noise_s;
+    *ctx->htp = tp;  // (stage 1 has retired: eval_device waited for it)
+    HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, ctx->s_main));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // diagnostics (GAPLAC_TAIL_TRACE): "N M ms" of the covariance launches alone, appended to <trace path>.pc
+    const bool timed = !ctx->ttrace_path.empty();
+    if (timed) {
+        HIPCK(ctx, hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) {
+            (void)hipEventDestroy(ev[0]);
+            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
+        }
+        (void)hipEventRecord(ev[0], ctx->s_main);
+    }
+    LaunchGuard g;
+    g.base = ctx->A;
+    g.elems = (int64_t)ctx->A_elems;
+    g.base2 = ctx->B;
+    g.elems2 = (int64_t)ctx->B_elems;
+    {
+        GuardScope scope(&g);
+        // row M of B (the v row) carries the mean: its results are not used
+        launch_post_cov(ctx->s_main, ctx->A, lda, Np, N, M, ctx->B, ldb, ctx->dXs, M, ctx->pmean, ctx->dtp);
+    }
+    if (timed) {
+        float ms = 0.f;
+        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".pc").c_str(), "a") : nullptr) {
+            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)M, (double)ms);
+            std::fclose(f);
+        }
+    }
+    if (g.violations)
+        return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    HIPCK(ctx, hipGetLastError());
+    return 0;
+}
+
+// Stage 3: the factorisation of order M of the matrix in ctx->B (A and B already swapped by the
+// caller's WsSwap; xr_mode / xr_tiles set for riding rows). info > 0: the leading minor of Sigma*.
+int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, EvalResult* r) {
+    int rc = eval_device(ctx, M, D, tp, r);
+    if (rc) return rc;
+    if ((rc = finish(*r, nullptr, nullptr, nullptr)))
+        return set_err(ctx, rc, "the test-point covariance Sigma* is not positive definite (leading minor %d)", rc);
+    return 0;
+}
+
+int posterior_mean_cov_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                            const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                            int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (M < 0 || (out_cov && ldc < M)) return set_err(ctx, GAPLAC_E_ARG, "M = %lld < 0 or ldc < M", (long long)M);
+    for (int64_t j = 0; j < M; ++j) {  // (rows M .. ldc-1 of out_cov are the caller's)
+        if (out_mean) out_mean[j] = NAN;
+        if (out_cov)
+            for (int64_t i = 0; i < M; ++i) out_cov[j * ldc + i] = NAN;
+    }
+    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (M == 0) return 0;
+    if (N == 0) {  // the posterior of an empty FiniteGP is the prior
+        if (out_cov && (rc = gaplac_gram(ctx, M, D, Xs, ldxs, T, terms, noise_s, out_cov, ldc))) return rc;
+        for (int64_t j = 0; j < M && out_mean; ++j) out_mean[j] = 0.0;
+        return 0;
+    }
+    tp.noise = noise;
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, out_cov != nullptr))) return rc;
+    if (out_cov) {
+        const int64_t ldb = round_up(M + 1, NB);
+        LaunchGuard g;
+        g.base2 = ctx->B;
+        g.elems2 = (int64_t)ctx->B_elems;
+        {
+            GuardScope scope(&g);
+            launch_mirror_lower(ctx->s_main, ctx->B, ldb, M);
+        }
+        if (g.violations)
+            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+        HIPCK(ctx, hipGetLastError());
+        HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)ldb * 8, (size_t)M * 8, (size_t)M,
+                                    hipMemcpyDeviceToHost, ctx->s_main));
+    }
+    if (out_mean)
+        HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+int posterior_rand_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                        const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                        int64_t ldxs, double noise_s, int64_t R, const double* Z, int64_t ldz, double* out,
+                        int64_t ldo) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (M < 0 || R < 0 || !out || ldz < M || ldo < M || (R > 0 && M > 0 && !Z))
+        return set_err(ctx, GAPLAC_E_ARG, "M < 0, R < 0, Z / out NULL, or ldz / ldo < M");
+    for (int64_t r = 0; r < R; ++r)  // (rows M .. ldo-1 of out are the caller's)
+        for (int64_t i = 0; i < M; ++i) out[r * ldo + i] = NAN;
+    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (M == 0 || R == 0) return 0;
+    if (N == 0)  // the prior at the test points
+        return gaplac_rand_multi(ctx, M, D, Xs, ldxs, T, terms, noise_s, R, Z, ldz, out, ldo);
+    tp.noise = noise;
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, true))) return rc;
+    const int64_t Mp = round_up(M + 1, NB);
+    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Mp * (size_t)R))) return rc;
+    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)M * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Mp * 8, Z, (size_t)ldz * 8, (size_t)M * 8, (size_t)R,
+                                hipMemcpyHostToDevice, ctx->s_main));
+    WsSwap swap(ctx);  // from here on ctx->A is the order-M workspace
+    EvalResult r2;
+    if ((rc = joint_factor(ctx, M, D, tp, &r2))) return rc;
+    {
+        LaunchGuard g;
+        g.base = ctx->A;
+        g.elems = (int64_t)ctx->A_elems;
+        GuardScope scope(&g);
+        launch_lower_mm(ctx->s_main, ctx->A, Mp, M, ctx->dZ, Mp, R, ctx->dO, M);
+        launch_add_mean(ctx->s_main, ctx->dO, M, M, R, ctx->pmean);
+        if (g.violations)
+            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    }
+    HIPCK(ctx, hipGetLastError());
+    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)M * 8, (size_t)M * 8, (size_t)R,
+                                hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+int posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                          const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                          int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys, double* out_logpdf,
+                          double* out_logdet, double* out_quad) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (M < 0 || R < 0 || !out_logpdf || ldys < M || (R > 0 && M > 0 && !Ys))
+        return set_err(ctx, GAPLAC_E_ARG, "M < 0, R < 0, Ys / out_logpdf NULL, or ldys < M");
+    if (M > 0 && R > 0) {  // (an empty call writes nothing)
+        for (int64_t r = 0; r < R; ++r) {
+            out_logpdf[r] = NAN;
+            if (out_quad) out_quad[r] = NAN;
+        }
+        if (out_logdet) *out_logdet = NAN;
+    }
+    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (M == 0 || R == 0) return 0;
+    if (N == 0)  // the prior at the test points
+        return gaplac_logpdf_multi(ctx, M, D, Xs, ldxs, T, terms, noise_s, R, Ys, ldys, out_logpdf, out_logdet,
+                                   out_quad);
+    if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
+        return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
+    const int rt = (int)((R + NB - 1) / NB);
+    tp.noise = noise;
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, rt, true))) return rc;
+    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)M * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)M * 8, Ys, (size_t)ldys * 8, (size_t)M * 8, (size_t)R,
+                                hipMemcpyHostToDevice, ctx->s_main));
+    WsSwap swap(ctx);
+    // the rows hold (Ys - m 1^T)^T and ride along as the responses of gaplac_logpdf_multi do
+    ctx->xr_mode = 3;
+    ctx->xr_tiles = rt;
+    ctx->xr_M = R;
+    ctx->xr_Y = ctx->dY;
+    ctx->xr_ldy = M;
+    ctx->xr_sub = ctx->pmean;
+    EvalResult r2;
+    if ((rc = joint_factor(ctx, M, D, tp, &r2))) return rc;
+    if (out_logdet) *out_logdet = r2.logdet;
     if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
     HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
     return 0;
@@ -2146,6 +2401,76 @@ int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, in
                                 hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
     return 0;
+}
+
+int gaplac_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                              const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                              int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
+    return posterior_mean_cov_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, out_mean, out_cov,
+                                   ldc);
+}
+
+int gaplac_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                          const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                          int64_t ldxs, double noise_s, int64_t R, const double* Z, int64_t ldz, double* out,
+                          int64_t ldo) {
+    return posterior_rand_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, R, Z, ldz, out, ldo);
+}
+
+int gaplac_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                            const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                            int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
+                            double* out_logpdf, double* out_logdet, double* out_quad) {
+    return posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, R, Ys, ldys, out_logpdf,
+                                 out_logdet, out_quad);
+}
+
+// Host-only walk of the joint posterior's three stages (no device needed): the posterior
+// evaluation of order N with M test points, the covariance launches (zeroing, post_cov_kernel,
+// the mirroring pass) against both workspaces, and the preloaded factorisation of order M, with
+// R > 0 carrying R riding rows (gaplac_posterior_logpdf), else plain (gaplac_posterior_rand).
+// short_ws 1 / 2: the order-N / order-M workspace one element short (negative controls).
+int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                            int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || M < 1 || R < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
+    const int64_t Np = round_up(N + 1, NB), Mp = round_up(M + 1, NB);
+    const int mt = (int)((M + NB - 1) / NB), rt = (int)((R + NB - 1) / NB);
+    const int64_t lda = Np + (int64_t)NB * mt, ldb = Mp + (int64_t)NB * rt;
+    LaunchGuard g1, g2, g3;
+    gaplac_ctx c1;
+    c1.spw = spw;
+    c1.xr_mode = 2;
+    c1.xr_tiles = mt;
+    c1.xr_M = M;
+    int rc = dry_walk(c1, N, g1, short_ws == 1 ? 1 : 0);
+    if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
+    if (rc == 0) {
+        double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+        double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
+        g2.base = fa;
+        g2.elems = lda * Np - (short_ws == 1 ? 1 : 0);
+        g2.base2 = fb;
+        g2.elems2 = ldb * Mp - (short_ws == 2 ? 1 : 0);
+        g2.dry = true;
+        GuardScope scope(&g2);
+        launch_post_cov(nullptr, fa, lda, Np, N, M, fb, ldb, nullptr, M, nullptr, nullptr);
+        if (R == 0) launch_mirror_lower(nullptr, fb, ldb, M);
+    }
+    if (rc == 0) {
+        gaplac_ctx c3;
+        c3.spw = spw;
+        c3.preloaded = true;
+        c3.xr_mode = R > 0 ? 3 : 0;
+        c3.xr_tiles = rt;
+        c3.xr_M = R;
+        rc = dry_walk(c3, M, g3, short_ws == 2 ? 1 : 0);
+        if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
+    }
+    if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches;
+    if (out_violations) *out_violations = g1.violations + g2.violations + g3.violations;
+    const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.first;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+    return rc;
 }
 
 // Host-only walk of one evaluation's schedule (no device needed): every launch's element

@@ -194,6 +194,10 @@ void build_single_tail_list(int T, int X, int tail_sim, int workers, std::vector
 struct LaunchGuard {
     const double* base = nullptr;  // the guarded allocation (a context's column storage)
     int64_t elems = 0;
+    // a second guarded allocation (region 1 of guard_launch): the order-M workspace the joint
+    // posterior's covariance kernel writes while it reads the first
+    const double* base2 = nullptr;
+    int64_t elems2 = 0;
     bool dry = false;
     int64_t launches = 0;
     int64_t violations = 0;
@@ -215,8 +219,8 @@ struct GuardScope {
     ~GuardScope() { current_guard() = prev; }
 };
 // true if the launch may proceed: [p + lo, p + hi) inside the guard (when p is guarded,
-// i.e. derived from its base) and not a dry run
-bool guard_launch(const char* what, const double* p, int64_t lo, int64_t hi);
+// i.e. derived from its base) and not a dry run; region 1: against the guard's second allocation
+bool guard_launch(const char* what, const double* p, int64_t lo, int64_t hi, int region = 0);
 // launches that touch no guarded storage: counted, skipped in a dry run
 bool guard_launch(const char* what);
 
@@ -315,9 +319,22 @@ void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, con
                      double* out);
 // ---- matrix forms: many vectors per factorisation ----
 // Extra rows Np .. Np + 128 mt - 1 = Y^T (Y is N x R, leading dimension ldy): mt x nt tiles,
-// zero outside response r < R and observation i < N.
+// zero outside response r < R and observation i < N; sub (or nullptr): N values subtracted from
+// every column on the way.
 void launch_rows_from_matrix(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t R, int mt,
-                             const double* Y, int64_t ldy);
+                             const double* Y, int64_t ldy, const double* sub = nullptr);
+// ---- joint posterior at test points ----
+// After a posterior evaluation (V^T in the extra rows of A, lda = Np + 128 ceil(M/128)): zeroes
+// V^T's columns [N, Np), then B = the augmented matrix of Sigma* = gram(Xs, noise_s) - V^T V for
+// a factorisation of order M: lower 128x128 tiles of the Mp x Mp matrix (Mp = roundup(M+1, 128),
+// leading dimension ldb >= Mp), row M = v (M values), zero padding. dtp: the pack with noise =
+// noise_s. Checked against the guard's first allocation (A) and its second (B).
+void launch_post_cov(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t N, int64_t M, double* B, int64_t ldb,
+                     const double* Xs, int64_t ldxs, const double* v, const TermPack* dtp);
+// B's strict upper triangle (order M) = its lower triangle, in place (the guard's second allocation).
+void launch_mirror_lower(hipStream_t s, double* B, int64_t ldb, int64_t M);
+// O[:, c] += mean, c < R (O is M x R, leading dimension ldo).
+void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean);
 // After the factorisation and launch_reduce (same stream): quad_r = sum_k W^T[r,k]^2 and
 // logpdf_r = -(N log 2pi + res->logdet + quad_r) / 2 (partial: ceil(N/512) * R doubles).
 void launch_quad_rows(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t R,

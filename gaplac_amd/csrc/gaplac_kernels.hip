@@ -2393,9 +2393,11 @@ __global__ __launch_bounds__(256) void lower_mv_reduce_kernel(const double* __re
 // Response rows: tile (E, J) of the extra rows = Y^T, A[i lda + Np + r] = Y[i + r ldy], 0
 // outside r < R, i < N. Reads run along i, writes along r: each 128 x 128 tile goes through
 // LDS in four strips of 32 columns of A (row stride NB + 1: both sides conflict-free).
+// sub (or nullptr): a vector of N subtracted from every column of Y on the way (the held-out
+// responses minus the posterior mean, gaplac_posterior_logpdf).
 __global__ __launch_bounds__(256) void rows_from_matrix_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
                                                                int64_t N, int64_t R, const double* __restrict__ Y,
-                                                               int64_t ldy) {
+                                                               int64_t ldy, const double* __restrict__ sub) {
     __shared__ double t[32][NB + 1];
     const int tid = threadIdx.x;
     const int64_t i0 = (int64_t)blockIdx.x * NB, r0 = (int64_t)blockIdx.y * NB;
@@ -2403,11 +2405,13 @@ __global__ __launch_bounds__(256) void rows_from_matrix_kernel(double* __restric
         {
             const int ii = tid & 31, rq = tid >> 5;
             const int64_t i = i0 + 32 * s + ii;
+            const double si = (sub && i < N) ? sub[i] : 0.0;
 #pragma unroll 4
             for (int it = 0; it < NB / 8; ++it) {
                 const int rr = rq + 8 * it;
                 const int64_t r = r0 + rr;
-                t[ii][rr] = (i < N && r < R) ? Y[i + r * ldy] : 0.0;
+                const double y = (i < N && r < R) ? Y[i + r * ldy] : 0.0;
+                t[ii][rr] = sub ? y - si : y;
             }
         }
         __syncthreads();
@@ -2553,6 +2557,102 @@ __global__ __launch_bounds__(256, 2) void lower_mm_kernel(const double* __restri
                 if (i < N && c < R) O[c * ldo + i] = acc[ni][mj][rg];
             }
     }
+}
+
+// ---------------------------------------------------------------------------------
+// Joint posterior at test points (AbstractGPs mean_and_cov / rand / logpdf of
+// posterior(fx, y)(xs, noise_s)): Sigma* = gram(Xs, noise_s) - V^T V from the rows V^T the
+// posterior evaluation left below the factor, written as the augmented matrix of a second
+// factorisation (order M) into its own workspace B.
+// ---------------------------------------------------------------------------------
+
+// V^T[:, N .. Np) = 0 over the `rows` extra rows: column N was updated against the v row and
+// the padding columns against unit pivots; neither is part of V^T (post_cov_kernel sums k < Np).
+__global__ __launch_bounds__(256) void zero_xrow_cols_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                             int64_t N, int64_t rows) {
+    const int64_t col = N + blockIdx.y;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (col < Np && r < rows) A[col * lda + Np + r] = 0.0;
+}
+
+// One workgroup = one 128x128 lower tile (bi >= bj) of B. The tile starts as the test points'
+// Gram tile (gram_tile over Xs with the pack's noise = noise_s: the diagonal rule, row M = v,
+// zero padding), built in the MMA staging LDS and stored; the workgroup reads it back as its
+// accumulators and runs the negated fp64 MFMA chain acc -= V^T[bi rows, k] V^T[bj rows, k] over
+// k = 0 .. Np-1 in ascending order (columns k >= N hold zeros: zero_xrow_cols_kernel). The extra
+// rows are column-major in k: row j of V^T is A[k lda + Np + j], so P / Q are the tile rows'
+// offsets with ldp = lda. One accumulator chain per element, K never split: an entry does not
+// depend on M or on where its points stand. Tile row mt (M a multiple of 128: the v row and
+// the padding only) has no V^T rows and stays as gram_tile wrote it.
+__global__ __launch_bounds__(256, 2) void post_cov_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                          int mt, double* __restrict__ B, int64_t ldb, int64_t M,
+                                                          const double* __restrict__ Xs, int64_t ldxs,
+                                                          const double* __restrict__ v,
+                                                          const TermPack* __restrict__ tpp) {
+    __shared__ MmaLds sm;
+    int bi, bj;
+    tri_index(blockIdx.x, bi, bj);
+    gram_tile(B + (int64_t)bj * NB * ldb, ldb, M, Xs, ldxs, v, tpp, bi, bj, reinterpret_cast<double*>(&sm));
+    if (bi >= mt) return;
+    __syncthreads();  // the tile's stores are complete (and the LDS free) before any wave reads it back
+    double* __restrict__ Ct = B + (int64_t)bj * NB * ldb + (int64_t)bi * NB;
+    const double* __restrict__ P = A + Np + (int64_t)bi * NB;
+    const double* __restrict__ Q = A + Np + (int64_t)bj * NB;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    const int wi = w & 1, wj = w >> 1;
+    const bool active = !(bi == bj && wj > wi);
+    const int fr = lane >> 4, fc = lane & 15;
+    d4 acc[4][4];
+    if (active) {
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const double* Ci = Ct + 64 * wi + 16 * mi + fc;
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg)
+                    acc[mi][mj][rg] = Ci[(int64_t)(64 * wj + 16 * mj + fr + 4 * rg) * ldb];
+        }
+    }
+    tile_mma_neg<KB>(P, Q, lda, (int)Np, active, acc, sm);
+    if (!active) return;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        double* Ci = Ct + 64 * wi + 16 * mi + fc;
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg)
+                Ci[(int64_t)(64 * wj + 16 * mj + fr + 4 * rg) * ldb] = acc[mi][mj][rg];
+    }
+}
+
+// B's strict upper triangle (rows, columns < M) = its lower triangle, in place: 32x32 blocks
+// (by >= bx) through LDS, so both sides run along a column. The result's two triangles are
+// mirror images bit for bit. Only for gaplac_posterior_mean_cov: nothing factors B afterwards.
+__global__ __launch_bounds__(256) void mirror_lower_kernel(double* __restrict__ B, int64_t ldb, int64_t M) {
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    if (by < bx) return;
+    __shared__ double t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t r0 = (int64_t)by * 32, c0 = (int64_t)bx * 32;
+    for (int cc = ty; cc < 32; cc += 8)  // t[cc][rr] = B(r0 + rr, c0 + cc)
+        t[cc][tx] = (r0 + tx < M && c0 + cc < M) ? B[(c0 + cc) * ldb + r0 + tx] : 0.0;
+    __syncthreads();
+    for (int rr = ty; rr < 32; rr += 8) {  // B(c0 + cc, r0 + rr) = B(r0 + rr, c0 + cc), cc = tx
+        const int64_t i = c0 + tx, j = r0 + rr;
+        if (i < j && j < M) B[j * ldb + i] = t[tx][rr];
+    }
+}
+
+// O[:, c] += mean for every column c < R (the draws of gaplac_posterior_rand: m 1^T + L* Z).
+__global__ __launch_bounds__(256) void add_mean_kernel(double* __restrict__ O, int64_t ldo, int64_t M, int64_t R,
+                                                       const double* __restrict__ mean) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M) return;
+    const double m = mean[i];
+    for (int64_t c = blockIdx.y; c < R; c += gridDim.y) O[c * ldo + i] += m;
 }
 
 // =================================================================================
@@ -3509,17 +3609,19 @@ LaunchGuard*& current_guard() {
     return g;
 }
 
-bool guard_launch(const char* what, const double* p, int64_t lo, int64_t hi) {
+bool guard_launch(const char* what, const double* p, int64_t lo, int64_t hi, int region) {
     LaunchGuard* g = current_guard();
     if (!g) return true;
     ++g->launches;
-    if (g->base) {
-        const int64_t off = (int64_t)(((intptr_t)p - (intptr_t)g->base) / (intptr_t)sizeof(double));
-        if (lo > hi || off + lo < 0 || off + hi > g->elems) {
+    const double* base = region ? g->base2 : g->base;
+    const int64_t elems = region ? g->elems2 : g->elems;
+    if (base) {
+        const int64_t off = (int64_t)(((intptr_t)p - (intptr_t)base) / (intptr_t)sizeof(double));
+        if (lo > hi || off + lo < 0 || off + hi > elems) {
             if (g->violations++ == 0) {
                 char buf[200];
                 snprintf(buf, sizeof buf, "%s touches elements [%lld, %lld) of a %lld-element workspace", what,
-                         (long long)(off + lo), (long long)(off + hi), (long long)g->elems);
+                         (long long)(off + lo), (long long)(off + hi), (long long)elems);
                 g->first = buf;
             }
             return false;
@@ -3831,10 +3933,41 @@ void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, con
 }
 
 void launch_rows_from_matrix(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t R, int mt,
-                             const double* Y, int64_t ldy) {
+                             const double* Y, int64_t ldy, const double* sub) {
     if (nt <= 0 || mt <= 0) return;
     if (!guard_launch("rows_from_matrix_kernel", A, 0, ((int64_t)nt * NB - 1) * lda + Np + (int64_t)mt * NB)) return;
-    rows_from_matrix_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, R, Y, ldy);
+    rows_from_matrix_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, R, Y, ldy, sub);
+}
+
+void launch_post_cov(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t N, int64_t M, double* B, int64_t ldb,
+                     const double* Xs, int64_t ldxs, const double* v, const TermPack* dtp) {
+    if (M <= 0 || N <= 0) return;
+    const int64_t mt = (M + NB - 1) / NB, Mp = (M + NB) / NB * NB, ntb = Mp / NB;
+    const int64_t rows = mt * NB;
+    // the kernel sums whole staging chunks up to Np: the columns [N, Np) of the extra rows are zeroed first
+    if (guard_launch("zero_xrow_cols_kernel", A, N * lda + Np, (Np - 1) * lda + Np + rows))
+        zero_xrow_cols_kernel<<<dim3((unsigned)((rows + 255) / 256), (unsigned)(Np - N)), dim3(256), 0, s>>>(A, lda, Np,
+                                                                                                          N, rows);
+    // reads the extra rows of every column of A; writes the lower tiles of B (tile rows 0 .. ntb-1)
+    const bool a_ok = guard_launch("post_cov_kernel (extra rows)", A, Np, (Np - 1) * lda + Np + rows);
+    const bool b_ok = guard_launch("post_cov_kernel", B, 0, tiles_end(ldb, ntb - 1, ntb - 1), 1);
+    if (!a_ok || !b_ok) return;
+    post_cov_kernel<<<dim3((unsigned)(ntb * (ntb + 1) / 2)), dim3(256), 0, s>>>(A, lda, Np, (int)mt, B, ldb, M, Xs,
+                                                                               ldxs, v, dtp);
+}
+
+void launch_mirror_lower(hipStream_t s, double* B, int64_t ldb, int64_t M) {
+    if (M <= 0) return;
+    if (!guard_launch("mirror_lower_kernel", B, 0, (M - 1) * ldb + M, 1)) return;
+    const unsigned nb = (unsigned)((M + 31) / 32);
+    mirror_lower_kernel<<<dim3(nb, nb), dim3(256), 0, s>>>(B, ldb, M);
+}
+
+void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean) {
+    if (M <= 0 || R <= 0) return;
+    if (!guard_launch("add_mean_kernel")) return;
+    add_mean_kernel<<<dim3((unsigned)((M + 255) / 256), (unsigned)std::min<int64_t>(R, 65535)), dim3(256), 0, s>>>(
+        O, ldo, M, R, mean);
 }
 
 void launch_quad_rows(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t R,

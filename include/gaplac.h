@@ -201,6 +201,48 @@ int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, in
                       int32_t T, const gaplac_term* terms, double noise,
                       int64_t R, const double* Z, int64_t ldz, double* out, int64_t ldo);
 
+/* Joint posterior at M test points: with C = K(X) + noise I = L L^T, V = L^{-1} K(X, xs) and
+ * z = L^{-1} y,
+ *     m = V^T z,   Sigma* = gram(Xs, terms, noise_s) - V^T V = L* L*^T
+ * where gram(Xs, terms, noise_s) is the test points' own Gram matrix as gaplac_gram builds it
+ * (noise_s on the diagonal; a NOISE term adds its variance on the diagonal only and is 0 across
+ * the two point sets). m is the mean gaplac_posterior_mean_var returns. One factorisation of
+ * order N (the posterior evaluation), one fp64-MFMA kernel for Sigma* and, for rand / logpdf, a
+ * second factorisation of order M of the matrix that kernel left in device memory.
+ * Common convention: every output is NaN-filled first; info > 0 when either Cholesky fails
+ * (all outputs stay NaN; gaplac_last_error names the matrix: the training covariance, or the
+ * test-point covariance with info = the 1-based leading minor of Sigma*). GAPLAC_E_ARG for
+ * noise_s < 0 or non-finite, M < 0, R < 0, a leading dimension below M, a NULL matrix of
+ * positive size, out / out_logpdf NULL. M = 0 or R = 0: 0 after the argument and term checks,
+ * nothing written. N = 0: the posterior is the prior at the test points (mean 0, gaplac_gram,
+ * gaplac_rand_multi, gaplac_logpdf_multi on (Xs, noise_s)). GAPLAC_E_OOM when the two
+ * workspaces do not fit (no chunking). The context stays usable after every failure.
+ *
+ * mean_cov: m (M values) and the full symmetric Sigma* (M x M column-major, leading dimension
+ * ldc; both triangles written, exact mirror images; rows M .. ldc-1 untouched). Either output
+ * may be NULL. No second factorisation: an indefinite Sigma* is returned as it is.
+ * Replaces: mean_and_cov(posterior(fx, y)(xs, noise_s)) of AbstractGPs 0.5.12. */
+int gaplac_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                              int32_t T, const gaplac_term* terms, double noise, const double* y,
+                              int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                              double* out_mean, double* out_cov, int64_t ldc);
+/* rand: out = m 1^T + L* Z for the M x R standard-normal matrix Z the caller drew (leading
+ * dimension ldz); out is M x R (ldo; rows M .. ldo-1 untouched). A column's sample depends
+ * neither on R nor on the column's position.
+ * Replaces: rand(rng, posterior(fx, y)(xs, noise_s), R). */
+int gaplac_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                          int32_t T, const gaplac_term* terms, double noise, const double* y,
+                          int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                          int64_t R, const double* Z, int64_t ldz, double* out, int64_t ldo);
+/* logpdf: out_logpdf[r] = -(M log 2pi + logdet Sigma* + |L*^{-1} (Ys[:, r] - m)|^2) / 2 for the
+ * M x R matrix Ys of held-out responses (ldys); out_logdet (one value) and out_quad (R values)
+ * may be NULL. Replaces: logpdf(posterior(fx, y)(xs, noise_s), Ys). */
+int gaplac_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                            int32_t T, const gaplac_term* terms, double noise, const double* y,
+                            int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                            int64_t R, const double* Ys, int64_t ldys,
+                            double* out_logpdf, double* out_logdet, double* out_quad);
+
 /* Debug / parity entries (tests only; not on the timed path). */
 /* Gram matrix sum_t K_t(X) + noise*I as a dense N×N column-major host matrix
  * (replaces KernelFunctions.kernelmatrix + Diagonal(Fill(noise, N))). */
@@ -277,6 +319,13 @@ int gaplac_reset_stats(gaplac_ctx* ctx);
  * Not in the reference (an internal guard). */
 int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* out_launches,
                       int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for the joint posterior entries: the posterior evaluation of order N with M
+ * test points, the covariance launches against both workspaces, and the second factorisation
+ * of order M (R > 0: with R riding rows, as gaplac_posterior_logpdf; R = 0: plain, as
+ * gaplac_posterior_rand). short_ws 1 / 2: the order-N / order-M workspace one element short
+ * (the negative controls); 0: as allocated. Not in the reference. */
+int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_t short_ws,
+                            int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* Host-only accounting of the single-GPU schedule for order N (GAPLAC_SPW = spw,
  * GAPLAC_PAIR_DEPTH = depth (0: auto), band extension pair_ext (0/1), GAPLAC_PAIR_M =
  * pair_m): every tile column gets every earlier panel column exactly once, in order, before

@@ -6,6 +6,9 @@
 //                                which also builds / checks every tail task list
 //                                (build_tail_tasks, sim_order_tail_tasks, check_tail_tasks,
 //                                interleave_tail_tasks) on its first call;
+//   gaplac_plan_check_joint    - the joint posterior's three stages (the posterior evaluation,
+//                                the covariance launches against both workspaces, the
+//                                preloaded factorisation of order M, plain or with riding rows);
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -55,6 +58,24 @@ int main() {
         const int rc = gaplac_plan_check(N, 11, 64, 4, &a, &b, msg, sizeof msg);
         EXPECT(rc == 0 && b >= 1, "negative control (mode 11) N=%lld not reported", (long long)N);
     }
+    // the joint posterior: stages 1-3, then each workspace one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t M : {1, 127, 128, 129, 1000, 10300})
+            for (int64_t R : {0, 1, 130})
+                for (int64_t N : sizes) {
+                    const int rc = gaplac_plan_check_joint(N, M, R, spw, 0, &a, &b, msg, sizeof msg);
+                    EXPECT(rc == 0 && a > 0 && b == 0, "plan_check_joint N=%lld M=%lld R=%lld spw=%d: rc %d violations %lld %s",
+                           (long long)N, (long long)M, (long long)R, spw, rc, (long long)b, msg);
+                    ++checks;
+                }
+    for (int short_ws : {1, 2})
+        for (int64_t N : {1, 128, 300, 4096})
+            for (int64_t R : {0, 5}) {
+                const int rc = gaplac_plan_check_joint(N, 129, R, 4, short_ws, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && b >= 1, "negative control (joint, short_ws %d) N=%lld R=%lld not reported", short_ws,
+                       (long long)N, (long long)R);
+            }
+    EXPECT(gaplac_plan_check_joint(10, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "joint: M = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
