@@ -31,6 +31,7 @@ EXPORTED = (
     "gaplac_logpdf_grad",
     "gaplac_logpdf_grad_device",
     "gaplac_posterior_mean_var",
+    "gaplac_posterior_components",
     "gaplac_rand",
     "gaplac_logpdf_multi",
     "gaplac_logpdf_multi_device",
@@ -155,6 +156,9 @@ def load() -> ctypes.CDLL:
     lib.gaplac_logpdf_grad.argtypes = common + [_DP, c_void_p, c_void_p, _DP]
     lib.gaplac_logpdf_grad_device.argtypes = common + [_DP, c_void_p, c_void_p, _DP]
     lib.gaplac_posterior_mean_var.argtypes = common + [c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.gaplac_posterior_components.argtypes = common + [
+        c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+    ]
     lib.gaplac_rand.argtypes = common + [c_void_p]
     # (the matrix forms take R, the matrix and its leading dimension where `common` ends in v)
     multi = common[:-1] + [c_int64, c_void_p, c_int64]

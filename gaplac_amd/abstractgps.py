@@ -132,6 +132,16 @@ class PosteriorGP:
         ctx = self.ctx or backend.default_context()
         return ctx.posterior_mean_var(self.prior.x, self.prior.terms, self.prior.noise, self.y, self._xs(x))
 
+    def component_mean_and_var(self, x, comp, G=None):
+        """(mean[M, G], var[M, G]) of every component of the kernel at the rows of x: comp[t] is
+        the component of lowered term t (kernels.lower_formula_components gives the map of a
+        formula's summands), -1 for none. One factorisation for all of them
+        (gaplac_posterior_components); nothing in AbstractGPs does this in one call."""
+        _gate()
+        ctx = self.ctx or backend.default_context()
+        return ctx.posterior_components(self.prior.x, self.prior.terms, self.prior.noise, self.y, self._xs(x),
+                                        comp, G)
+
     def mean(self, x):
         return self.mean_and_var(x)[0]
 

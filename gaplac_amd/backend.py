@@ -197,6 +197,39 @@ class Context:
         self._check(rc)
         return mean, var
 
+    def posterior_components(self, X, terms, noise: float, y, Xs, comp, G=None):
+        """(mean[M, G], var[M, G]): the posterior of every component of k = sum_g k_g at the
+        rows of Xs, all from one factorisation (gaplac_posterior_components). comp[t] is the
+        component of term t (-1: none; equal within a product group); G defaults to
+        max(comp) + 1."""
+        Xc = _colmajor(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, D = Xc.shape
+        if y.shape[0] != N:
+            raise ArgumentError(f"length of y ({y.shape[0]}) != N ({N})")
+        Xsc = _colmajor(Xs)
+        M = Xsc.shape[0]
+        if Xsc.shape[1] != D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {D}")
+        terms = list(terms)
+        comp = [int(c) for c in comp]
+        if len(comp) != len(terms):
+            raise ArgumentError(f"comp has {len(comp)} entries for {len(terms)} terms")
+        if G is None:
+            G = max(comp, default=-1) + 1
+        G = int(G)
+        ta = term_array(terms)
+        ca = (c_int32 * max(1, len(comp)))(*comp)
+        mean = np.empty((M, max(G, 0)), dtype=np.float64, order="F")
+        var = np.empty((M, max(G, 0)), dtype=np.float64, order="F")
+        rc = self.lib.gaplac_posterior_components(
+            self.h, N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+            y.ctypes.data_as(c_void_p), M, Xsc.ctypes.data_as(c_void_p), max(M, 1), G, ca,
+            mean.ctypes.data_as(c_void_p), max(M, 1), var.ctypes.data_as(c_void_p), max(M, 1),
+        )
+        self._check(rc)
+        return mean, var
+
     def rand(self, X, terms, noise: float, z):
         """L z with C = K(X) + noise I = L L^T (gaplac_rand): one draw of the FiniteGP for the
         standard-normal vector z."""

@@ -158,7 +158,11 @@ struct gaplac_ctx {
     int xr_mode = 0;
     int xr_tiles = 0;
     int64_t xr_M = 0;       // mode 2: test points; mode 3: responses R
-    double* dXs = nullptr;  // mode 2: test inputs (ld M)
+    double* dXs = nullptr;  // mode 2: test inputs (ld M; per-component rows: ld xr_sel.Mc)
+    // mode 2, gaplac_posterior_components (§10.7): the xr_M = G * Mc rows are packed components,
+    // built and finished per row by the selector; everything between sees xr_M ordinary rows
+    bool xr_comp = false;
+    CompSel xr_sel{};
     size_t dXs_elems = 0;
     const double* xr_Y = nullptr;  // mode 3: the responses on the device (dY, or the caller's matrix), ld xr_ldy
     int64_t xr_ldy = 0;
@@ -1055,7 +1059,7 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     if (ctx->xr_mode == 1) launch_init_identity_rows(ctx->s_main, ctx->A, lda, Np, nt, ctx->spw);
     if (ctx->xr_mode == 2)
         launch_cross_gram(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->dX, N, ctx->dXs,
-                          ctx->xr_M, ctx->dtp);
+                          ctx->xr_comp ? ctx->xr_sel.Mc : ctx->xr_M, ctx->dtp, ctx->xr_comp ? &ctx->xr_sel : nullptr);
     if (ctx->xr_mode == 3)
         launch_rows_from_matrix(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->xr_Y,
                                 ctx->xr_ldy, ctx->xr_sub);
@@ -1066,8 +1070,9 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     int rc;
     if ((rc = factor_and_reduce(ctx, N, lda, nt))) return rc;
     if (ctx->xr_mode == 2)
-        launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dXs, ctx->xr_M, ctx->dtp, ctx->gpart,
-                         ctx->pmean, ctx->pvar);
+        launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dXs,
+                         ctx->xr_comp ? ctx->xr_sel.Mc : ctx->xr_M, ctx->dtp, ctx->gpart, ctx->pmean, ctx->pvar,
+                         ctx->xr_comp ? &ctx->xr_sel : nullptr);
     if (ctx->xr_mode == 3)
         launch_quad_rows(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dres, ctx->gpart, ctx->mres,
                          ctx->mres ? ctx->mres + ctx->xr_M : nullptr /* (a dry walk has no buffers) */);
@@ -1445,6 +1450,93 @@ int posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64
     if (rc) return rc;
     if (out_mean) HIPCK(ctx, hipMemcpy(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost));
     if (out_var) HIPCK(ctx, hipMemcpy(out_var, ctx->pvar, (size_t)M * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Body of gaplac_posterior_components: the posterior evaluation with the
+// G components' cross-covariances as G * M packed riding rows (xr_mode 2 with the selector).
+int posterior_components_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                              const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                              int64_t ldxs, int32_t G, const int32_t* comp, double* out_mean, int64_t ldm,
+                              double* out_var, int64_t ldv) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (G < 0 || M < 0 || (out_mean && ldm < M) || (out_var && ldv < M))
+        return set_err(ctx, GAPLAC_E_ARG, "G < 0, M < 0, or ldm / ldv < M");
+    for (int32_t g = 0; g < G; ++g)
+        for (int64_t j = 0; j < M; ++j) {
+            if (out_mean) out_mean[g * ldm + j] = NAN;
+            if (out_var) out_var[g * ldv + j] = NAN;
+        }
+    int rc = check_common(ctx, N, D, X, ldx, noise, y);
+    if (rc) return rc;
+    if (M > 0 && D > 0 && (!Xs || ldxs < M)) return set_err(ctx, GAPLAC_E_ARG, "Xs NULL / ldxs < M");
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (G > 0 && T > 0 && !comp) return set_err(ctx, GAPLAC_E_ARG, "comp is NULL");
+    CompSel sel{};
+    sel.Mc = M;
+    sel.G = G;
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) sel.comp[t] = -1;
+    for (int t = 0; comp && t < T; ++t) {
+        if (comp[t] < -1 || comp[t] >= G)
+            return set_err(ctx, GAPLAC_E_ARG, "comp[%d] = %d outside [-1, %d)", t, comp[t], G);
+        sel.comp[t] = comp[t];
+    }
+    for (int t = 0; comp && t + 1 < T; ++t)
+        if (!tp.last_in_group[t] && comp[t] != comp[t + 1])
+            return set_err(ctx, GAPLAC_E_KIND, "terms %d and %d: one product group in two components", t, t + 1);
+    if (G == 0 || M == 0) return 0;
+    if (M > ((int64_t)65535 * NB) / G)  // the cross-covariance grid's tile rows
+        return set_err(ctx, GAPLAC_E_OOM, "G * M = %d * %lld rows exceed 65535 tile rows", G, (long long)M);
+    const int64_t R = (int64_t)G * M;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if (N == 0) {  // the prior per component: mean 0, var kdiag_g
+        for (int32_t g = 0; g < G; ++g)
+            for (int64_t j = 0; j < M; ++j) {
+                double kd = 0.0, pr = 1.0;
+                for (int t = 0; t < T; ++t) {
+                    const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : Xs[(int64_t)tp.col[t] * ldxs + j];
+                    double k = 1.0;
+                    if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
+                    if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
+                    pr *= sel.comp[t] == g ? k : 0.0;
+                    if (tp.last_in_group[t]) {
+                        kd += pr;
+                        pr = 1.0;
+                    }
+                }
+                if (out_mean) out_mean[g * ldm + j] = 0.0;
+                if (out_var) out_var[g * ldv + j] = kd;
+            }
+        return 0;
+    }
+    if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
+    const size_t nxs = (size_t)M * (size_t)(D > 0 ? D : 1);
+    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, nxs))) return rc;
+    if (D > 0)
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)M * 8, Xs, (size_t)ldxs * 8, (size_t)M * 8, (size_t)D,
+                                    hipMemcpyHostToDevice, ctx->s_main));
+    tp.noise = noise;
+    ctx->xr_mode = 2;
+    ctx->xr_tiles = (int)((R + NB - 1) / NB);
+    ctx->xr_M = R;
+    ctx->xr_comp = true;
+    ctx->xr_sel = sel;
+    EvalResult r;
+    rc = eval_device(ctx, N, D, tp, &r);
+    ctx->xr_mode = 0;
+    ctx->xr_tiles = 0;
+    ctx->xr_comp = false;
+    if (rc) return rc;
+    rc = finish(r, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    // (pmean / pvar hold the G columns packed, leading dimension M)
+    if (out_mean)
+        HIPCK(ctx, hipMemcpy2D(out_mean, (size_t)ldm * 8, ctx->pmean, (size_t)M * 8, (size_t)M * 8, (size_t)G,
+                               hipMemcpyDeviceToHost));
+    if (out_var)
+        HIPCK(ctx, hipMemcpy2D(out_var, (size_t)ldv * 8, ctx->pvar, (size_t)M * 8, (size_t)M * 8, (size_t)G,
+                               hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2291,6 +2383,14 @@ int gaplac_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
                               const gaplac_term* terms, double noise, const double* y, int64_t M,
                               const double* Xs, int64_t ldxs, double* out_mean, double* out_var) {
     return posterior_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, out_mean, out_var);
+}
+
+int gaplac_posterior_components(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
+                                int64_t ldxs, int32_t G, const int32_t* comp, double* out_mean, int64_t ldm,
+                                double* out_var, int64_t ldv) {
+    return posterior_components_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, G, comp, out_mean, ldm,
+                                     out_var, ldv);
 }
 
 int gaplac_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,

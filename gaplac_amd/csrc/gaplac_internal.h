@@ -26,6 +26,16 @@ struct TermPack {
     double  noise;                 // FiniteGP observation variance (diagonal)
 };
 
+// Component selector of the per-component posterior, passed to its two
+// kernels by value: riding row r = g * Mc + j is test point j of component g, whose kernel
+// is the sum over the product groups with comp == g (-1: the term is in no component; all
+// terms of a group carry the same value).
+struct CompSel {
+    int64_t Mc;  // test points per component
+    int32_t G;   // components; the evaluation carries G * Mc riding rows
+    int32_t comp[GAPLAC_MAX_TERMS];
+};
+
 // Device-side result record of one evaluation.
 constexpr int REDUCE_BLOCKS = 64;  // workgroups of the logdet / quad reduction
 struct EvalResult {
@@ -308,12 +318,15 @@ void launch_grad_contract(hipStream_t s, const double* A, int64_t lda, int64_t N
 // Extra rows Np .. Np + 128 mt - 1 (lda = Np + 128 mt) = K(xs, X): mt x nt tiles, zero
 // outside test point j < M and training point i < N.
 void launch_cross_gram(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t M, int mt,
-                       const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp);
+                       const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp,
+                       const CompSel* sel = nullptr);
+// (sel, both launchers: the rows are the packed components of §10.7, M = sel->G * sel->Mc rows, Xs
+// holds sel->Mc points; the same grids and footprints, cross_gram_comp_kernel / post_finish_comp_kernel)
 // After the factorisation: mean_j = sum_k V^T[j,k] z_k, var_j = kdiag(xs_j) - sum_k V^T[j,k]^2
 // (partial: 2 * ceil(N/512) * M doubles).
 void launch_posterior(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t M,
                       const double* Xs, int64_t ldxs, const TermPack* dtp, double* partial, double* mean,
-                      double* var);
+                      double* var, const CompSel* sel = nullptr);
 // ---- rand(FiniteGP): out = L z over the factor's lower triangle (partial: ceil(N/512) * N) ----
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,
                      double* out);

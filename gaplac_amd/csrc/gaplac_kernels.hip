@@ -2345,6 +2345,106 @@ __global__ __launch_bounds__(256) void post_finish_kernel(const double* __restri
 }
 
 // ---------------------------------------------------------------------------------
+// Per-component posteriors: G components of a formula k = sum_g k_g as
+// G Mc packed riding rows of one factorisation, row r = g Mc + j = K_g(xs_j, X), K_g the sum
+// over the product groups with sel.comp == g. The factorisation and post_partial_kernel see
+// G Mc ordinary rows; only the row contents and the prior variance know about components.
+// A term outside the row's component contributes the factor 0 (as an index-noise term does
+// across point sets), so its group's product is exactly 0 and the sums keep
+// cross_gram_kernel's / post_finish_kernel's operations and order: with every term in
+// component 0 the rows and variances are theirs bit for bit.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cross_gram_comp_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                              int64_t N, const double* __restrict__ X, int64_t ldx,
+                                                              const double* __restrict__ Xs, int64_t ldxs,
+                                                              const TermPack* __restrict__ tpp, const CompSel sel) {
+    __shared__ double xcol[GAPLAC_MAX_TERMS][NB];
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    const int J = (int)blockIdx.x, E = (int)blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t c0 = (int64_t)J * NB;
+    for (int idx = tid; idx < T * NB; idx += 256) {
+        const int t = idx / NB, c = idx % NB;
+        xcol[t][c] = (c0 + c < N && tp.kind[t] != GAPLAC_NOISE) ? X[(int64_t)tp.col[t] * ldx + c0 + c] : 0.0;
+    }
+    // rows r0, r0 + 1 (one double2 store); each has its own component and test point
+    const int64_t R = (int64_t)sel.G * sel.Mc;
+    const int64_t r0 = (int64_t)E * NB + 2 * lane;
+    const bool ok0 = r0 < R, ok1 = r0 + 1 < R;
+    const int64_t ga = ok0 ? r0 / sel.Mc : -2, gb = ok1 ? (r0 + 1) / sel.Mc : -2;  // (-2: no component's)
+    const int64_t ja = ok0 ? r0 - ga * sel.Mc : 0, jb = ok1 ? r0 + 1 - gb * sel.Mc : 0;
+    double xa[GAPLAC_MAX_TERMS], xb[GAPLAC_MAX_TERMS];
+    bool sa[GAPLAC_MAX_TERMS], sb[GAPLAC_MAX_TERMS];
+#pragma unroll
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+        xa[t] = 0.0;
+        xb[t] = 0.0;
+        sa[t] = t < T && tp.kind[t] != GAPLAC_NOISE && sel.comp[t] == ga;
+        sb[t] = t < T && tp.kind[t] != GAPLAC_NOISE && sel.comp[t] == gb;
+        if (t < T && tp.kind[t] != GAPLAC_NOISE) {
+            const double* xc = Xs + (int64_t)tp.col[t] * ldxs;
+            if (ok0) xa[t] = xc[ja];
+            if (ok1) xb[t] = xc[jb];
+        }
+    }
+    __syncthreads();
+    double* base = A + c0 * lda + Np + r0;
+    for (int cc = w; cc < NB; cc += 4) {
+        double tot0 = 0.0, tot1 = 0.0, pr0 = 1.0, pr1 = 1.0;
+#pragma unroll
+        for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+            if (t < T) {
+                const int kind = tp.kind[t];
+                const double p = tp.p[t], xj = xcol[t][cc];
+                pr0 *= sa[t] ? term_k(kind, p, xa[t], xj, false) : 0.0;
+                pr1 *= sb[t] ? term_k(kind, p, xb[t], xj, false) : 0.0;
+                if (tp.last_in_group[t]) {
+                    tot0 += pr0;
+                    tot1 += pr1;
+                    pr0 = 1.0;
+                    pr1 = 1.0;
+                }
+            }
+        }
+        const bool colok = c0 + cc < N;
+        const double o0 = (colok && ok0) ? tot0 : 0.0, o1 = (colok && ok1) ? tot1 : 0.0;
+        *reinterpret_cast<double2*>(base + (int64_t)cc * lda) = make_double2(o0, o1);
+    }
+}
+
+// mean_r, var_r = kdiag_g(xs_j) - sum of the partials (fixed order), r = g Mc + j; a NOISE
+// term of component g counts with its variance.
+__global__ __launch_bounds__(256) void post_finish_comp_kernel(const double* __restrict__ pm,
+                                                               const double* __restrict__ pv, int nk,
+                                                               const double* __restrict__ Xs, int64_t ldxs,
+                                                               const TermPack* __restrict__ tpp, const CompSel sel,
+                                                               double* __restrict__ mean, double* __restrict__ var) {
+    const int64_t R = (int64_t)sel.G * sel.Mc;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int64_t g = r / sel.Mc, j = r - g * sel.Mc;
+    const TermPack& tp = *tpp;
+    double kd = 0.0, pr = 1.0;
+    for (int t = 0; t < tp.T; ++t) {
+        const int kind = tp.kind[t];
+        const double x = kind == GAPLAC_NOISE ? 0.0 : Xs[(int64_t)tp.col[t] * ldxs + j];
+        pr *= sel.comp[t] == g ? term_k(kind, tp.p[t], x, x, true) : 0.0;
+        if (tp.last_in_group[t]) {
+            kd += pr;
+            pr = 1.0;
+        }
+    }
+    double m = 0.0, v = 0.0;
+    for (int y = 0; y < nk; ++y) {
+        m += pm[(int64_t)y * R + r];
+        v += pv[(int64_t)y * R + r];
+    }
+    mean[r] = m;
+    var[r] = kd - v;
+}
+
+// ---------------------------------------------------------------------------------
 // rand(FiniteGP) (AbstractGPs: m + cholesky(C).U' * randn): out = L z
 // over the factor's lower triangle (k <= i: the diagonal tiles' upper parts hold junk).
 // ---------------------------------------------------------------------------------
@@ -3902,15 +4002,21 @@ void build_grad_list(int m, std::vector<uint32_t>& out) {
 }
 
 void launch_cross_gram(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t M, int mt,
-                       const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp) {
+                       const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp,
+                       const CompSel* sel) {
     if (nt <= 0 || mt <= 0) return;
     if (!guard_launch("cross_gram_kernel", A, 0, ((int64_t)nt * NB - 1) * lda + Np + (int64_t)mt * NB)) return;
-    cross_gram_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, M, X, ldx, Xs, ldxs, dtp);
+    if (sel)  // the same mt x nt tiles, the rows built per component (M = sel->G * sel->Mc)
+        cross_gram_comp_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, X, ldx, Xs, ldxs,
+                                                                                      dtp, *sel);
+    else
+        cross_gram_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, M, X, ldx, Xs, ldxs,
+                                                                                 dtp);
 }
 
 void launch_posterior(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t M,
                       const double* Xs, int64_t ldxs, const TermPack* dtp, double* partial, double* mean,
-                      double* var) {
+                      double* var, const CompSel* sel) {
     if (M <= 0) return;
     if (!guard_launch("post_partial_kernel", A, 0, (N - 1) * lda + Np + M)) return;
     const int nk = (int)((N + 511) / 512);
@@ -3918,8 +4024,12 @@ void launch_posterior(hipStream_t s, const double* A, int64_t lda, int64_t Np, i
     double* pv = partial + (size_t)nk * M;
     post_partial_kernel<<<dim3((unsigned)((M + 255) / 256), (unsigned)nk), dim3(256), 0, s>>>(A, lda, Np, N, M, pm,
                                                                                             pv);
-    post_finish_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s>>>(pm, pv, M, nk, Xs, ldxs, dtp, mean,
-                                                                             var);
+    if (sel)
+        post_finish_comp_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s>>>(pm, pv, nk, Xs, ldxs, dtp,
+                                                                                      *sel, mean, var);
+    else
+        post_finish_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s>>>(pm, pv, M, nk, Xs, ldxs, dtp,
+                                                                                 mean, var);
 }
 
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,

@@ -328,3 +328,61 @@ def lower_formula(formula: F.GPCompnent, hyperparams=None, products: bool = Fals
                 out.append(_lower_leaf(kk.compose(SelectTransform((pos + 1,))), g))
                 pos += 1
     return out, vars_
+
+
+# --------------------------------------------------------------------------- components
+
+
+def _num_text(v) -> str:
+    return repr(int(v)) if float(v) == int(v) else repr(float(v))
+
+
+def formula_text(node: F.GPCompnent) -> str:
+    """A formula (sub)tree written back in the formula syntax (defaults omitted)."""
+    if isinstance(node, F.GPOperation):
+        if node.op == "add":
+            return f"{formula_text(node.lhs)} + {formula_text(node.rhs)}"
+        parts = []
+        for side in (node.lhs, node.rhs):
+            s = formula_text(side)
+            parts.append(f"({s})" if isinstance(side, F.GPOperation) and side.op == "add" else s)
+        return " * ".join(parts)
+    if isinstance(node, F.Noise):
+        return "Noise" if node.variance == 1.0 else f"Noise({_num_text(node.variance)})"
+    name = type(node).__name__
+    if isinstance(node, (F.SqExp, F.OU)) and node.lengthscale != 1:
+        return f"{name}(:{node.varname}; l={_num_text(node.lengthscale)})"
+    if isinstance(node, F.Linear) and node.intercept != 0:
+        return f"{name}(:{node.varname}; c={_num_text(node.intercept)})"
+    return f"{name}(:{node.varname})"
+
+
+def _summands(node: F.GPCompnent) -> List[F.GPCompnent]:
+    if isinstance(node, F.GPOperation) and node.op == "add":
+        return _summands(node.lhs) + _summands(node.rhs)
+    return [node]
+
+
+def lower_formula_components(formula: F.GPCompnent, hyperparams=None, products: bool = False):
+    """(terms, vars, comp, labels) for gaplac_posterior_components: lower_formula's terms and
+    variables, the component of every term and one label per component.
+
+    A component is a top-level summand of the formula as written and its label the summand's
+    text (a `Noise` summand is a component of its own). products=True: a product summand is
+    one product group and one component. products=False (the reference lowering): every
+    lowered term is one summand, hence its own component, except that a formula that is a
+    single top-level product is ONE component: kernel() turns that product into a sum (Q1),
+    and all of its summed terms belong to the one summand the user wrote.
+    """
+    terms, vars_ = lower_formula(formula, hyperparams, products=products)
+    parts = _summands(formula)
+    labels = [formula_text(p) for p in parts]
+    if products:
+        comp = [t[3] for t in terms]  # the product group is the summand's index
+    elif len(parts) == 1:
+        comp = [0] * len(terms)
+    else:
+        if len(terms) != len(parts):  # (kernel() rejects a product inside a sum before this)
+            raise RuntimeError(f"{len(terms)} lowered terms for {len(parts)} summands")
+        comp = list(range(len(terms)))
+    return terms, vars_, comp, labels

@@ -157,6 +157,34 @@ int gaplac_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
                               int64_t M, const double* Xs, int64_t ldxs,
                               double* out_mean, double* out_var);
 
+/* Per-component posteriors at M test points (the arithmetic of the reference's `fitplot`
+ * command, "the posteriors of different components of the GP"): for a formula k = sum_g k_g,
+ *     mean_g(xs_j) = K_g(xs_j, X) C^{-1} y
+ *     var_g(xs_j)  = k_g(xs_j, xs_j) - K_g(xs_j, X) C^{-1} K_g(X, xs_j)
+ * with C = K(X) + noise I built from every term and K_g from component g's terms only. All G
+ * components ride one factorisation as G*M extra rows. comp has T entries: comp[t] in [0, G) is
+ * the component of term t, -1 puts the term in none; all terms of one product group must carry
+ * the same value (GAPLAC_E_KIND otherwise). out_mean / out_var are M x G column-major (leading
+ * dimensions ldm / ldv; rows M .. ld-1 are never written); either may be NULL. A component
+ * without terms is the zero process (mean and variance exactly +0.0); a component made of a
+ * NOISE term has mean exactly 0 and the term's variance; the observation noise belongs to no
+ * component. The component means sum to gaplac_posterior_mean_var's mean when every non-NOISE
+ * term is in a component.
+ * Same return convention as gaplac_posterior_mean_var: every output entry is NaN-filled first
+ * and stays NaN on a PosDefException (info > 0); the context stays usable after every failure.
+ * GAPLAC_E_ARG also for G < 0, comp NULL with G > 0 and T > 0, an entry outside [-1, G),
+ * ldm < M or ldv < M for a non-NULL output. G = 0 or M = 0: 0 after the argument and term
+ * checks, nothing written. N = 0: the prior (mean 0, variance kdiag_g). GAPLAC_E_OOM when
+ * ceil(G*M/128) > 65535 or the rows do not fit in device memory beside the matrix (no chunking).
+ * Replaces: mean_and_var(posterior(FiniteGP(GP(k), X, noise), y) with the kernel k_g, xs) per
+ *           component, as the reference's unimplemented `fitplot` (README) would need; nothing
+ *           in AbstractGPs 0.5.12 does it in one call. */
+int gaplac_posterior_components(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                                int32_t T, const gaplac_term* terms, double noise, const double* y,
+                                int64_t M, const double* Xs, int64_t ldxs,
+                                int32_t G, const int32_t* comp,
+                                double* out_mean, int64_t ldm, double* out_var, int64_t ldv);
+
 /* One draw of the FiniteGP: out = L z with C = K(X) + noise I = L L^T
  * and z the N standard-normal values the caller drew (the host keeps the RNG stream, so a
  * given z gives the same sample as the reference). Replaces: rand(rng, FiniteGP(GP(k), X,
@@ -307,8 +335,9 @@ int gaplac_reset_stats(gaplac_ctx* ctx);
 
 /* Launch-footprint check of one evaluation's schedule, on the host only (no device, no
  * context): walks every launch gaplac_logpdf (mode 0), gaplac_logpdf_grad (mode 1) or
- * gaplac_posterior_mean_var at M test points (mode 2) or gaplac_logpdf_multi of M responses
- * (mode 3) would enqueue for order N with
+ * gaplac_posterior_mean_var at M test points (mode 2; also gaplac_posterior_components, whose
+ * G components at M' points are M = G*M' rows behind the same launchers) or gaplac_logpdf_multi
+ * of M responses (mode 3) would enqueue for order N with
  * super-panel width spw, and checks the element range each launch's grid touches against
  * the workspace the context allocates for N. Every launcher applies the same check before
  * a real launch (a violating launch is not enqueued; the entry returns GAPLAC_E_ARG).

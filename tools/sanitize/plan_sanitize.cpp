@@ -58,6 +58,19 @@ int main() {
         const int rc = gaplac_plan_check(N, 11, 64, 4, &a, &b, msg, sizeof msg);
         EXPECT(rc == 0 && b >= 1, "negative control (mode 11) N=%lld not reported", (long long)N);
     }
+    // gaplac_posterior_components: G * M packed rows through the posterior's launchers (mode 2 at
+    // M = G * M), at the row counts of tests/test_gpu_components.py; mode 10: the
+    // same walk against the short workspace
+    for (int64_t rows : {231, 645, 510, 600, 258, 6144, 6147})
+        for (int64_t N : {1, 50, 127, 128, 129, 300, 513, 700, 16384}) {
+            int rc = gaplac_plan_check(N, 2, rows, 4, &a, &b, msg, sizeof msg);
+            EXPECT(rc == 0 && a > 0 && b == 0, "plan_check (component rows) N=%lld rows=%lld: rc %d violations %lld %s",
+                   (long long)N, (long long)rows, rc, (long long)b, msg);
+            rc = gaplac_plan_check(N, 10, rows, 4, &a, &b, msg, sizeof msg);
+            EXPECT(rc == 0 && b >= 1, "negative control (mode 10) N=%lld rows=%lld not reported", (long long)N,
+                   (long long)rows);
+            ++checks;
+        }
     // the joint posterior: stages 1-3, then each workspace one element short
     for (int spw : {1, 4, 8})
         for (int64_t M : {1, 127, 128, 129, 1000, 10300})
