@@ -39,6 +39,9 @@ EXPORTED = (
     "gaplac_posterior_mean_cov",
     "gaplac_posterior_rand",
     "gaplac_posterior_logpdf",
+    "gaplac_sparse_elbo",
+    "gaplac_sparse_posterior_mean_var",
+    "gaplac_sparse_split",
     "gaplac_gram",
     "gaplac_gram_time",
     "gaplac_factor",
@@ -48,6 +51,7 @@ EXPORTED = (
     "gaplac_plan_check",
     "gaplac_plan_check_schedule",
     "gaplac_plan_check_joint",
+    "gaplac_plan_check_sparse",
     "gaplac_dist_create",
     "gaplac_dist_destroy",
     "gaplac_dist_last_error",
@@ -170,6 +174,13 @@ def load() -> ctypes.CDLL:
     lib.gaplac_posterior_mean_cov.argtypes = joint + [c_void_p, c_void_p, c_int64]
     lib.gaplac_posterior_rand.argtypes = joint + [c_int64, c_void_p, c_int64, c_void_p, c_int64]
     lib.gaplac_posterior_logpdf.argtypes = joint + [c_int64, c_void_p, c_int64, c_void_p, _DP, c_void_p]
+    # (the sparse entries: `common`, then Mz, Z, ldz, jitter)
+    sparse = common + [c_int64, c_void_p, c_int64, c_double]
+    lib.gaplac_sparse_elbo.argtypes = sparse + [_DP, _DP, _DP, _DP, _DP]
+    lib.gaplac_sparse_posterior_mean_var.argtypes = sparse + [c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.gaplac_sparse_split.argtypes = [c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]
+    lib.gaplac_plan_check_sparse.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
+                                             POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_gram.argtypes = [
         c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Term), c_double, c_void_p, c_int64,
     ]

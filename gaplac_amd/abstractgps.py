@@ -184,9 +184,82 @@ class FinitePosteriorGP:
         return self._ctx(ctx).posterior_logpdf(*self._args(), ys, full=full)
 
 
-def posterior(fx: FiniteGP, y, ctx: backend.Context | None = None) -> PosteriorGP:
-    """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8)."""
-    return PosteriorGP(fx, y, ctx)
+class VFE:
+    """AbstractGPs.VFE(fz): the inducing-point approximation of Titsias with pseudo-points
+    fz = f(z, jitter), a FiniteGP whose inputs are the inducing inputs and whose noise is the
+    jitter."""
+
+    def __init__(self, fz: FiniteGP):
+        if not isinstance(fz, FiniteGP):
+            raise F.ArgumentError("VFE takes the FiniteGP f(z, jitter) at the inducing inputs")
+        self.fz = fz
+
+
+def _vfe_args(vfe: VFE, fx: FiniteGP, y):
+    if not isinstance(vfe, VFE) or not isinstance(fx, FiniteGP):
+        raise F.ArgumentError("expected (VFE(f(z)), f(x, noise), y)")
+    if vfe.fz.terms != fx.terms:
+        raise F.ArgumentError("VFE: f(z) and f(x) must be the same GP")
+    if vfe.fz.x.shape[1] != fx.x.shape[1]:
+        raise F.ArgumentError("DimensionMismatch: inducing inputs and training inputs differ in columns")
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.shape[0] != len(fx):
+        raise F.ArgumentError("DimensionMismatch: length of y does not match the FiniteGP")
+    return fx.x, fx.terms, fx.noise, y, vfe.fz.x, vfe.fz.noise
+
+
+def elbo(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None, full: bool = False):
+    """AbstractGPs.elbo(VFE(f(z)), f(x, noise), y): the evidence lower bound (gaplac_sparse_elbo);
+    full=True returns the dict elbo, dtc, trace, logdet, quad."""
+    _gate()
+    args = _vfe_args(vfe, fx, y)
+    return (ctx or backend.default_context()).sparse_elbo(*args, full=full)
+
+
+def dtc(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):
+    """AbstractGPs.dtc(VFE(f(z)), f(x, noise), y): log N(y | 0, Q + noise I), the bound without
+    its trace term (gaplac_sparse_elbo's out_dtc)."""
+    _gate()
+    args = _vfe_args(vfe, fx, y)
+    return (ctx or backend.default_context()).sparse_elbo(*args, full=True)["dtc"]
+
+
+class ApproxPosteriorGP:
+    """AbstractGPs.posterior(VFE(f(z)), f(x, noise), y): the approximate posterior. Evaluation
+    happens per query, one gaplac_sparse_posterior_mean_var call each."""
+
+    def __init__(self, vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):
+        self._args = _vfe_args(vfe, fx, y)
+        self.approx = vfe
+        self.prior = fx
+        self.y = self._args[3]
+        self.ctx = ctx
+
+    def mean_and_var(self, x):
+        _gate()
+        X = np.asarray(x, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        ctx = self.ctx or backend.default_context()
+        return ctx.sparse_posterior_mean_var(*self._args, X)
+
+    def mean(self, x):
+        return self.mean_and_var(x)[0]
+
+    def var(self, x):
+        return self.mean_and_var(x)[1]
+
+
+def posterior(*args, ctx: backend.Context | None = None):
+    """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8), or
+    posterior(VFE(f(z)), fx, y): the approximate posterior of the inducing-point approximation."""
+    if args and isinstance(args[0], VFE):
+        if len(args) not in (3, 4):
+            raise F.ArgumentError("posterior(VFE(f(z)), fx, y)")
+        return ApproxPosteriorGP(args[0], args[1], args[2], args[3] if len(args) == 4 else ctx)
+    if len(args) not in (2, 3):
+        raise F.ArgumentError("posterior(fx, y)")
+    return PosteriorGP(args[0], args[1], args[2] if len(args) == 3 else ctx)
 
 
 def mean_and_var(f: PosteriorGP, x):

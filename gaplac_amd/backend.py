@@ -378,6 +378,56 @@ class Context:
         self._check(rc)
         return (lp[:R], ld.value, q[:R]) if full else lp[:R]
 
+    def _sparse_head(self, X, terms, noise, y, Z, jitter):
+        """The argument head the two sparse entries share (after self.h)."""
+        Xc = _colmajor(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, D = Xc.shape
+        if y.ndim != 1 or y.shape[0] != N:
+            raise ArgumentError(f"length of y ({y.shape[0] if y.ndim else 0}) != N ({N})")
+        Zc = _colmajor(Z)
+        Mz = Zc.shape[0]
+        if Zc.shape[1] != D:
+            raise ArgumentError(f"inducing inputs have {Zc.shape[1]} columns, training inputs {D}")
+        terms = list(terms)
+        ta = term_array(terms)
+        head = (N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+                y.ctypes.data_as(c_void_p), Mz, Zc.ctypes.data_as(c_void_p), max(Mz, 1), float(jitter))
+        return head, (Xc, y, Zc, ta), D
+
+    def sparse_elbo(self, X, terms, noise: float, y, Z, jitter: float = 0.0, full: bool = False):
+        """The evidence lower bound of the inducing-point (VFE) approximation with inducing inputs
+        Z (gaplac_sparse_elbo); full=True returns the dict elbo, dtc, trace, logdet, quad."""
+        head, keep, _ = self._sparse_head(X, terms, noise, y, Z, jitter)
+        out = [c_double() for _ in range(5)]
+        rc = self.lib.gaplac_sparse_elbo(self.h, *head, *(byref(o) for o in out))
+        self._check(rc)
+        names = ("elbo", "dtc", "trace", "logdet", "quad")
+        return {k: o.value for k, o in zip(names, out)} if full else out[0].value
+
+    def sparse_posterior_mean_var(self, X, terms, noise: float, y, Z, jitter: float, Xs):
+        """(mean, var) of the approximate posterior given y at the rows of Xs
+        (gaplac_sparse_posterior_mean_var)."""
+        head, keep, D = self._sparse_head(X, terms, noise, y, Z, jitter)
+        Xsc = _colmajor(Xs)
+        Ms = Xsc.shape[0]
+        if Xsc.shape[1] != D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {D}")
+        mean = np.empty(Ms, dtype=np.float64)
+        var = np.empty(Ms, dtype=np.float64)
+        mb = mean if Ms else np.empty(1)  # (an empty result still passes valid pointers)
+        vb = var if Ms else np.empty(1)
+        rc = self.lib.gaplac_sparse_posterior_mean_var(self.h, *head, Ms, Xsc.ctypes.data_as(c_void_p), max(Ms, 1),
+                                                       mb.ctypes.data_as(c_void_p), vb.ctypes.data_as(c_void_p))
+        self._check(rc)
+        return mean, var
+
+    def sparse_split(self, N: int, Mz: int):
+        """(chunks, chunk_rows) of the product over the N rows (gaplac_sparse_split)."""
+        chunks, rows = c_int64(), c_int64()
+        self._check(self.lib.gaplac_sparse_split(int(N), int(Mz), byref(chunks), byref(rows)))
+        return chunks.value, rows.value
+
     def gram(self, X, terms, noise: float = 0.0) -> np.ndarray:
         Xc = _colmajor(X)
         N, D = Xc.shape

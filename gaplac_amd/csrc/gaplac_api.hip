@@ -185,6 +185,11 @@ struct gaplac_ctx {
     size_t B_elems = 0;
     bool preloaded = false;
     const double* xr_sub = nullptr;  // mode 3: N values subtracted from every response (or nullptr)
+    // Inducing-point approximation: y on the device and the chunk partials of S
+    double* sp_y = nullptr;
+    size_t sp_y_elems = 0;
+    double* sp_part = nullptr;
+    size_t sp_part_elems = 0;
     // gradient: alpha, partial sums, the XCD-balanced C^{-1} tile list
     double* galpha = nullptr;
     size_t galpha_elems = 0;
@@ -267,7 +272,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        buf(&c->gout, gout_bytes), buf(&c->hgout, gout_bytes, true), buf(&c->dgp, sizeof(GradTermPack)),
                        buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist), large(&c->dY, &c->dY_elems),
                        buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems),
-                       large(&c->B, &c->B_elems)};
+                       large(&c->B, &c->B_elems), large(&c->sp_y, &c->sp_y_elems),
+                       large(&c->sp_part, &c->sp_part_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -1698,12 +1704,14 @@ int joint_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t
 }
 
 // Stage 3: the factorisation of order M of the matrix in ctx->B (A and B already swapped by the
-// caller's WsSwap; xr_mode / xr_tiles set for riding rows). info > 0: the leading minor of Sigma*.
-int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, EvalResult* r) {
+// caller's WsSwap; xr_mode / xr_tiles set for riding rows). info > 0: the leading minor of Sigma*
+// (or of the matrix `what` names: the sparse entries factor their S the same way, §10.8).
+int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, EvalResult* r,
+                 const char* what = "the test-point covariance Sigma*") {
     int rc = eval_device(ctx, M, D, tp, r);
     if (rc) return rc;
     if ((rc = finish(*r, nullptr, nullptr, nullptr)))
-        return set_err(ctx, rc, "the test-point covariance Sigma* is not positive definite (leading minor %d)", rc);
+        return set_err(ctx, rc, "%s is not positive definite (leading minor %d)", what, rc);
     return 0;
 }
 
@@ -1836,6 +1844,251 @@ int posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
     if (out_logdet) *out_logdet = r2.logdet;
     if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
     HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- inducing-point (VFE) approximation ----
+// The K-split of the stage-2 product: chunks of chunk_rows rows, a function of (N, Mz) alone
+// (never of the device, its free CUs or timing), so a call's summation order is fixed. Chunks
+// are SPARSE_CHUNK rows unless that would make more than SPARSE_PART_TILES partial tiles
+// (1 GiB of partials); then whole multiples of SPARSE_CHUNK. At N = 16384 .. 262144 and Mz =
+// 256 .. 4096 that is 96 .. 7854 workgroups of at least 1024 rows each.
+constexpr int64_t SPARSE_CHUNK = 1024;
+constexpr int64_t SPARSE_PART_TILES = 8192;
+void sparse_split(int64_t N, int64_t Mz, int64_t* chunks, int64_t* chunk_rows) {
+    const int64_t ntb = round_up(Mz + 1, NB) / NB, ntl = ntb * (ntb + 1) / 2;
+    const int64_t max_chunks = std::max<int64_t>(1, SPARSE_PART_TILES / ntl);
+    const int64_t blocks = (N + SPARSE_CHUNK - 1) / SPARSE_CHUNK;
+    const int64_t rows = SPARSE_CHUNK * std::max<int64_t>(1, (blocks + max_chunks - 1) / max_chunks);
+    *chunk_rows = rows;
+    *chunks = (N + rows - 1) / rows;
+}
+
+// k(x_j, x_j) of row j of a host matrix (the prior variance; a NOISE term counts).
+double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j) {
+    double kd = 0.0, pr = 1.0;
+    for (int t = 0; t < tp.T; ++t) {
+        const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + j];
+        double k = 1.0;
+        if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
+        if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
+        pr *= k;
+        if (tp.last_in_group[t]) {
+            kd += pr;
+            pr = 1.0;
+        }
+    }
+    return kd;
+}
+
+// Argument checks the two entries share, after their own (output pointers).
+int sparse_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise, const double* y,
+                 int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs) {
+    int rc = check_common(ctx, N, D, X, ldx, noise, y);
+    if (rc) return rc;
+    if (!(noise > 0.0)) return set_err(ctx, GAPLAC_E_PARAM, "noise %g must be > 0", noise);
+    if (!(jitter >= 0.0) || !std::isfinite(jitter))
+        return set_err(ctx, GAPLAC_E_PARAM, "jitter %g must be finite and >= 0", jitter);
+    if (Mz < 0 || (Mz > 0 && D > 0 && (!Z || ldz < Mz)))
+        return set_err(ctx, GAPLAC_E_ARG, "Mz = %lld < 0, or Z NULL / ldz %lld < Mz", (long long)Mz, (long long)ldz);
+    if (Ms < 0 || (Ms > 0 && D > 0 && (!Xs || ldxs < Ms)))
+        return set_err(ctx, GAPLAC_E_ARG, "Ms = %lld < 0, or Xs NULL / ldxs %lld < Ms", (long long)Ms, (long long)ldxs);
+    if (N > 0 && Mz > 0 && (N + Ms + NB - 1) / NB > 65535)  // (one grid row of the cross-covariance launch per tile row)
+        return set_err(ctx, GAPLAC_E_OOM, "N + Ms = %lld: more than 65535 tile rows in one call", (long long)(N + Ms));
+    return 0;
+}
+
+// Stages 1 and 2. Stage 1 is the posterior evaluation (xr_mode 2) of the training set (Z, jitter)
+// with v = 0 and the N rows of X, then the Ms rows of Xs, as its test points: V^T (and a_j^T)
+// below the factor, k(x, x) - |row|^2 in ctx->pvar; *trace = the sum of the first N of those, in
+// order. Stage 2 writes the augmented matrix of S into ctx->B, laid out for a factorisation of
+// order Mz with rows_tiles extra tile rows. tp carries noise = sigma^2 (the pack of stage 3).
+int sparse_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, const TermPack& tp,
+                  const double* y, int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms,
+                  const double* Xs, int64_t ldxs, int rows_tiles, double* trace) {
+    int rc;
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    const std::vector<double> zeros((size_t)Mz, 0.0);
+    if ((rc = upload(ctx, Mz, D, Z, ldz, zeros.data()))) return rc;
+    const int64_t R = N + Ms;
+    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, (size_t)R * (size_t)(D > 0 ? D : 1)))) return rc;
+    if (D > 0) {
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)R * 8, X, (size_t)ldx * 8, (size_t)N * 8, (size_t)D,
+                                    hipMemcpyHostToDevice, ctx->s_main));
+        if (Ms > 0)
+            HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs + N, (size_t)R * 8, Xs, (size_t)ldxs * 8, (size_t)Ms * 8, (size_t)D,
+                                        hipMemcpyHostToDevice, ctx->s_main));
+    }
+    if ((rc = ensure(ctx, &ctx->sp_y, &ctx->sp_y_elems, (size_t)N))) return rc;
+    HIPCK(ctx, hipMemcpyAsync(ctx->sp_y, y, (size_t)N * 8, hipMemcpyHostToDevice, ctx->s_main));
+    const int mt = (int)((R + NB - 1) / NB);
+    TermPack tp1 = tp;
+    tp1.noise = jitter;
+    ctx->xr_mode = 2;
+    ctx->xr_tiles = mt;
+    ctx->xr_M = R;
+    EvalResult r;
+    rc = eval_device(ctx, Mz, D, tp1, &r);
+    ctx->xr_mode = 0;
+    ctx->xr_tiles = 0;
+    if (rc) return rc;
+    if ((rc = finish(r, nullptr, nullptr, nullptr)))
+        return set_err(ctx, rc, "the inducing covariance K(Z) + jitter I is not positive definite (leading minor %d)", rc);
+    const int64_t Np = round_up(Mz + 1, NB), lda = Np + (int64_t)NB * mt;
+    const int64_t ldb = Np + (int64_t)NB * rows_tiles, ntb = Np / NB;
+    int64_t chunks, chunk_rows;
+    sparse_split(N, Mz, &chunks, &chunk_rows);
+    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)ldb * (size_t)Np))) return rc;
+    if ((rc = ensure(ctx, &ctx->sp_part, &ctx->sp_part_elems,
+                     (size_t)chunks * (size_t)(ntb * (ntb + 1) / 2) * (size_t)(NB * NB))))
+        return rc;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // diagnostics (GAPLAC_TAIL_TRACE): "N Mz ms" of the stage-2 launches alone, appended to <trace path>.ss
+    const bool timed = !ctx->ttrace_path.empty();
+    if (timed) {
+        HIPCK(ctx, hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) {
+            (void)hipEventDestroy(ev[0]);
+            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
+        }
+        (void)hipEventRecord(ev[0], ctx->s_main);
+    }
+    LaunchGuard g;
+    g.base = ctx->A;
+    g.elems = (int64_t)ctx->A_elems;
+    g.base2 = ctx->B;
+    g.elems2 = (int64_t)ctx->B_elems;
+    {
+        GuardScope scope(&g);
+        launch_rows_syrk(ctx->s_main, ctx->A, lda, Np, Mz, N, (int64_t)NB * mt, ctx->sp_y, chunks, chunk_rows,
+                         ctx->sp_part, ctx->B, ldb, tp.noise);
+    }
+    if (timed) {
+        float ms = 0.f;
+        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".ss").c_str(), "a") : nullptr) {
+            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)Mz, (double)ms);
+            std::fclose(f);
+        }
+    }
+    if (g.violations)
+        return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    HIPCK(ctx, hipGetLastError());
+    if (trace) {  // (stage 1 has retired: eval_device waited for it)
+        std::vector<double> pv((size_t)N);
+        HIPCK(ctx, hipMemcpy(pv.data(), ctx->pvar, (size_t)N * 8, hipMemcpyDeviceToHost));
+        double t = 0.0;
+        for (int64_t n = 0; n < N; ++n) t += pv[(size_t)n];
+        *trace = t;
+    }
+    return 0;
+}
+
+// Stage 3 is joint_factor on ctx->B (info > 0: the leading minor of S).
+constexpr const char* SPARSE_S = "S = noise I + V V^T";
+
+int sparse_elbo_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                     const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z, int64_t ldz,
+                     double jitter, double* out_elbo, double* out_dtc, double* out_trace, double* out_logdet,
+                     double* out_quad) {
+    if (!ctx) return GAPLAC_E_ARG;
+    for (double* o : {out_elbo, out_dtc, out_trace, out_logdet, out_quad})
+        if (o) *o = NAN;
+    if (!out_elbo) return set_err(ctx, GAPLAC_E_ARG, "out_elbo is NULL");
+    int rc = sparse_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, 0, nullptr, 0);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    tp.noise = noise;
+    const double log2pi = 1.8378770664093453;  // Julia's log2π
+    double trace = 0.0, logdet = 0.0, quad = 0.0, yty = 0.0;
+    for (int64_t n = 0; n < N; ++n) yty += y[n] * y[n];
+    if (N > 0 && Mz == 0) {  // Q = 0: the model is N(0, noise I), the trace the prior variances
+        for (int64_t n = 0; n < N; ++n) trace += host_kdiag(tp, X, ldx, n);
+        logdet = (double)N * std::log(noise);
+        quad = yty / noise;
+    } else if (N > 0) {
+        if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, 0, nullptr, 0, 0, &trace))) return rc;
+        WsSwap swap(ctx);  // from here on ctx->A is the workspace of S
+        EvalResult r2;
+        if ((rc = joint_factor(ctx, Mz, D, tp, &r2, SPARSE_S))) return rc;
+        logdet = (double)(N - Mz) * std::log(noise) + r2.logdet;
+        quad = (yty - r2.quad) / noise;
+    }
+    const double dtc = N > 0 ? -(((double)N * log2pi + logdet) + quad) / 2.0 : 0.0;
+    *out_elbo = N > 0 ? dtc - trace / (2.0 * noise) : 0.0;
+    if (out_dtc) *out_dtc = dtc;
+    if (out_trace) *out_trace = trace;
+    if (out_logdet) *out_logdet = logdet;
+    if (out_quad) *out_quad = quad;
+    return 0;
+}
+
+int sparse_posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                          const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                          int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs, double* out_mean,
+                          double* out_var) {
+    if (!ctx) return GAPLAC_E_ARG;
+    for (int64_t j = 0; j < Ms; ++j) {
+        if (out_mean) out_mean[j] = NAN;
+        if (out_var) out_var[j] = NAN;
+    }
+    int rc = sparse_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (Ms == 0) return 0;
+    if (N == 0 || Mz == 0) {  // no data, or Q = 0: the prior
+        for (int64_t j = 0; j < Ms; ++j) {
+            if (out_mean) out_mean[j] = 0.0;
+            if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
+        }
+        return 0;
+    }
+    tp.noise = noise;
+    const int rt = (int)((Ms + NB - 1) / NB);
+    if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, rt, nullptr))) return rc;
+    const int64_t Np = round_up(Mz + 1, NB);
+    const int64_t lda = Np + (int64_t)NB * ((N + Ms + NB - 1) / NB), ldb = Np + (int64_t)NB * rt;
+    // the a_j rows of stage 1, transposed, are the matrix whose columns ride stage 3 (xr_mode 3's row source)
+    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)Mz * (size_t)Ms))) return rc;
+    if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, 2 * (size_t)Ms * (size_t)((Mz + 511) / 512)))) return rc;
+    {
+        LaunchGuard g;
+        g.base = ctx->A;
+        g.elems = (int64_t)ctx->A_elems;
+        GuardScope scope(&g);
+        launch_rows_to_matrix(ctx->s_main, ctx->A, lda, Np, N, Mz, Ms, ctx->dY, Mz);
+        if (g.violations)
+            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    }
+    HIPCK(ctx, hipGetLastError());
+    WsSwap swap(ctx);
+    ctx->xr_mode = 3;
+    ctx->xr_tiles = rt;
+    ctx->xr_M = Ms;
+    ctx->xr_Y = ctx->dY;
+    ctx->xr_ldy = Mz;
+    EvalResult r2;
+    if ((rc = joint_factor(ctx, Mz, D, tp, &r2, SPARSE_S))) return rc;
+    {
+        // mode 2's reduction over the rows of stage 3: the dot with the v row (u) and the row norm
+        LaunchGuard g;
+        g.base = ctx->A;
+        g.elems = (int64_t)ctx->A_elems;
+        GuardScope scope(&g);
+        launch_sparse_post(ctx->s_main, ctx->A, ldb, Np, Mz, Ms, noise, ctx->gpart, ctx->pmean, ctx->pvar + N);
+        if (g.violations)
+            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    }
+    HIPCK(ctx, hipGetLastError());
+    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
+    if (out_var)
+        HIPCK(ctx, hipMemcpyAsync(out_var, ctx->pvar + N, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
     return 0;
 }
 
@@ -2523,6 +2776,88 @@ int gaplac_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double*
                             double* out_logpdf, double* out_logdet, double* out_quad) {
     return posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, R, Ys, ldys, out_logpdf,
                                  out_logdet, out_quad);
+}
+
+int gaplac_sparse_elbo(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                       const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                       int64_t ldz, double jitter, double* out_elbo, double* out_dtc, double* out_trace,
+                       double* out_logdet, double* out_quad) {
+    return sparse_elbo_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, out_elbo, out_dtc, out_trace,
+                            out_logdet, out_quad);
+}
+
+int gaplac_sparse_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                     const gaplac_term* terms, double noise, const double* y, int64_t Mz,
+                                     const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
+                                     int64_t ldxs, double* out_mean, double* out_var) {
+    return sparse_posterior_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, out_mean,
+                                 out_var);
+}
+
+int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {
+    if (N < 0 || Mz < 0 || !out_chunks || !out_chunk_rows) return GAPLAC_E_ARG;
+    sparse_split(N, Mz, out_chunks, out_chunk_rows);
+    return 0;
+}
+
+// Host-only walk of the sparse entries' three stages (no device needed): the posterior
+// evaluation of order Mz with N + Ms riding rows, the stage-2 launches (and, with Ms > 0, the
+// transposing copy) against both workspaces, and the preloaded factorisation of order Mz, plain
+// (Ms = 0, gaplac_sparse_elbo) or with Ms riding rows and their reduction
+// (gaplac_sparse_posterior_mean_var). short_ws 1 / 2: the stage-1 / stage-3 workspace one element
+// short (negative controls).
+int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                             int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || Mz < 1 || Ms < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
+    if ((N + Ms + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
+    const int64_t Np = round_up(Mz + 1, NB);
+    const int mt = (int)((N + Ms + NB - 1) / NB), rt = (int)((Ms + NB - 1) / NB);
+    const int64_t lda = Np + (int64_t)NB * mt, ldb = Np + (int64_t)NB * rt;
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    LaunchGuard g1, g2, g3, g4;
+    gaplac_ctx c1;
+    c1.spw = spw;
+    c1.xr_mode = 2;
+    c1.xr_tiles = mt;
+    c1.xr_M = N + Ms;
+    int rc = dry_walk(c1, Mz, g1, short_ws == 1 ? 1 : 0);
+    if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
+    if (rc == 0) {
+        g2.base = fa;
+        g2.elems = lda * Np - (short_ws == 1 ? 1 : 0);
+        g2.base2 = fb;
+        g2.elems2 = ldb * Np - (short_ws == 2 ? 1 : 0);
+        g2.dry = true;
+        GuardScope scope(&g2);
+        int64_t chunks, chunk_rows;
+        sparse_split(N, Mz, &chunks, &chunk_rows);
+        launch_rows_syrk(nullptr, fa, lda, Np, Mz, N, (int64_t)NB * mt, nullptr, chunks, chunk_rows, nullptr, fb, ldb,
+                         1.0);
+        launch_rows_to_matrix(nullptr, fa, lda, Np, N, Mz, Ms, nullptr, Mz);
+    }
+    if (rc == 0) {
+        gaplac_ctx c3;
+        c3.spw = spw;
+        c3.preloaded = true;
+        c3.xr_mode = Ms > 0 ? 3 : 0;
+        c3.xr_tiles = rt;
+        c3.xr_M = Ms;
+        rc = dry_walk(c3, Mz, g3, short_ws == 2 ? 1 : 0);
+        if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
+    }
+    if (rc == 0) {
+        g4.base = fb;
+        g4.elems = ldb * Np - (short_ws == 2 ? 1 : 0);
+        g4.dry = true;
+        GuardScope scope(&g4);
+        launch_sparse_post(nullptr, fb, ldb, Np, Mz, Ms, 1.0, nullptr, nullptr, nullptr);
+    }
+    if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches + g4.launches;
+    if (out_violations) *out_violations = g1.violations + g2.violations + g3.violations + g4.violations;
+    const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.violations ? g3.first : g4.first;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+    return rc;
 }
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior

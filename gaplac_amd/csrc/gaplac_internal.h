@@ -346,6 +346,24 @@ void launch_post_cov(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t 
                      const double* Xs, int64_t ldxs, const double* v, const TermPack* dtp);
 // B's strict upper triangle (order M) = its lower triangle, in place (the guard's second allocation).
 void launch_mirror_lower(hipStream_t s, double* B, int64_t ldb, int64_t M);
+// ---- inducing-point (VFE) approximation ----
+// After a posterior evaluation of order Mz (Np = roundup(Mz+1, 128)) whose `rows` riding rows
+// (a multiple of 128) start with the N rows of X: puts y (device, N values) into column Mz of
+// those rows and zeroes the columns beyond, then B = the augmented matrix of S = noise I +
+// (V^T)^T V^T for a factorisation of order Mz (lower tiles, leading dimension ldb >= Np, row Mz =
+// w = (V^T)^T y, zero padding) as the ascending sum of `chunks` partial products over chunk_rows
+// rows each (part: chunks * ntl * 128 * 128 doubles, ntl = the lower tiles of B). Checked
+// against the guard's first allocation (A) and its second (B).
+void launch_rows_syrk(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t N, int64_t rows,
+                      const double* y, int64_t chunks, int64_t chunk_rows, double* part, double* B, int64_t ldb,
+                      double noise);
+// Y (Mz x Ms, leading dimension ldy) = the transpose of the riding rows row0 .. row0 + Ms - 1.
+void launch_rows_to_matrix(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t row0, int64_t Mz,
+                           int64_t Ms, double* Y, int64_t ldy);
+// After the second factorisation (order Mz, Ms riding rows c_j^T = (L_S^{-1} a_j)^T, u in the v
+// row): mean_j = c_j . u, var_j += noise |c_j|^2 (partial: 2 * ceil(Mz/512) * Ms doubles).
+void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t Ms, double noise,
+                        double* partial, double* mean, double* var);
 // O[:, c] += mean, c < R (O is M x R, leading dimension ldo).
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean);
 // After the factorisation and launch_reduce (same stream): quad_r = sum_k W^T[r,k]^2 and

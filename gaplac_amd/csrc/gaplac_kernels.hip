@@ -2755,6 +2755,182 @@ __global__ __launch_bounds__(256) void add_mean_kernel(double* __restrict__ O, i
     for (int64_t c = blockIdx.y; c < R; c += gridDim.y) O[c * ldo + i] += m;
 }
 
+// ---------------------------------------------------------------------------------
+// Inducing-point (VFE) approximation (AbstractGPs elbo / dtc / posterior of
+// VFE(f(z))): the posterior evaluation of order Mz with the N rows of X (then the Ms rows of Xs)
+// riding leaves V^T = K(X, Z) L^{-T} below the factor, row n at A[k lda + Np + n], k < Mz: the
+// block is column-major, so the contraction index n of S = noise I + (V^T)^T V^T is the
+// contiguous one (post_cov_kernel contracts the same kind of block over k, the other
+// orientation). The product is a tall-skinny SYRK (K = N, an output of ceil((Mz+1)/128) tile
+// columns), split over K into chunks of whole rows whose partial tiles are summed in ascending
+// chunk order by a second kernel: no atomics, and the split is a function of (N, Mz) alone
+// (sparse_split, gaplac_api.hip), so a call is bitwise repeatable.
+// ---------------------------------------------------------------------------------
+
+// Column Mz of the riding rows = y for the rows n < N (0 for the rows of Xs and the tile's
+// padding), columns Mz+1 .. Np-1 = 0 (as zero_xrow_cols_kernel: column Mz was updated against
+// the v row and the padding columns against unit pivots; neither is part of V^T). With y there
+// the one product below also yields w = (V^T)^T y as row Mz of the result, the v row of the
+// second factorisation, in the same fixed order as S itself.
+__global__ __launch_bounds__(256) void sparse_rows_prep_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                               int64_t Mz, int64_t N, int64_t rows,
+                                                               const double* __restrict__ y) {
+    const int64_t col = Mz + blockIdx.y;
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (col < Np && r < rows) A[col * lda + Np + r] = (blockIdx.y == 0 && r < N) ? y[r] : 0.0;
+}
+
+// One workgroup = one 128x128 lower tile (bi >= bj) of the (Mz+1)-augmented product over one
+// chunk of rows n in [chunk chunk_rows, min(N, (chunk + 1) chunk_rows)): part[chunk][tile] =
+// sum_n R[n, bi rows] R[n, bj rows], R[n, i] = A[i lda + Np + n]. The chunk is staged RS_KC rows
+// of n at a time through registers (the next step's loads fly during this step's MFMAs) into
+// LDS as [i][n] with a row stride of RS_KC + 2 doubles, so that the MFMA operand reads (16
+// values of i x 2 of n per half wave) land on 32 distinct 8-byte banks; rows n >= the chunk's
+// end (the rows of Xs, which follow X's) are masked to 0 on the way. fp64 MFMA 16x16x4 with the
+// accumulator shape of tile_mma_neg: lane element (mi, mj, rg) of wave (wi, wj) is tile entry
+// (row 64 wi + 16 mi + (lane & 15), column 64 wj + 16 mj + (lane >> 4) + 4 rg). Every wave of a
+// diagonal tile computes (the tile comes out whole and symmetric bit for bit: an entry and its
+// mirror image are the same products in the same order). One accumulator chain per element in
+// ascending n. The partial tile is stored column-major (ld 128).
+constexpr int RS_KC = 16;
+constexpr int RS_LS = RS_KC + 2;
+constexpr int RS_RP = 512 / RS_KC;      // rows of i one staging pass of the 256 threads covers
+constexpr int RS_NP = NB / RS_RP;        // passes per operand
+__global__ __launch_bounds__(256, 2) void rows_syrk_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                           int64_t N, int64_t chunk_rows, double* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) double Ps[NB][RS_LS];
+    __shared__ __attribute__((aligned(16))) double Qs[NB][RS_LS];
+    int bi, bj;
+    tri_index(blockIdx.x, bi, bj);
+    const bool diag = bi == bj;
+    const int64_t n0 = (int64_t)blockIdx.y * chunk_rows;
+    const int64_t n1 = (n0 + chunk_rows) < N ? (n0 + chunk_rows) : N;
+    const double* __restrict__ P = A + Np + (int64_t)bi * NB * lda;
+    const double* __restrict__ Q = A + Np + (int64_t)bj * NB * lda;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    const int wi = w & 1, wj = w >> 1;
+    const int fr = lane >> 4, fc = lane & 15;
+    const int sn = 2 * (tid % (RS_KC / 2)), sr = tid / (RS_KC / 2);  // staging: rows n sn, sn + 1 of i = sr + RS_RP it
+    double2 preg[RS_NP], qreg[RS_NP];
+    auto fetch = [&](int64_t nb) {
+        const int64_t n = nb + sn;
+        const bool k0 = n < n1, k1 = n + 1 < n1;
+#pragma unroll
+        for (int it = 0; it < RS_NP; ++it) {
+            const int64_t off = (int64_t)(sr + RS_RP * it) * lda + n;
+            double2 v = *reinterpret_cast<const double2*>(P + off);
+            v.x = k0 ? v.x : 0.0;
+            v.y = k1 ? v.y : 0.0;
+            preg[it] = v;
+            if (!diag) {
+                double2 u = *reinterpret_cast<const double2*>(Q + off);
+                u.x = k0 ? u.x : 0.0;
+                u.y = k1 ? u.y : 0.0;
+                qreg[it] = u;
+            }
+        }
+    };
+    d4 acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj) acc[mi][mj] = d4{0.0, 0.0, 0.0, 0.0};
+    const double (*Qb)[RS_LS] = diag ? Ps : Qs;
+    const int nch = (int)((n1 - n0 + RS_KC - 1) / RS_KC);
+    if (nch > 0) fetch(n0);
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();  // every wave is done with the previous step
+#pragma unroll
+        for (int it = 0; it < RS_NP; ++it) {
+            *reinterpret_cast<double2*>(&Ps[sr + RS_RP * it][sn]) = preg[it];
+            if (!diag) *reinterpret_cast<double2*>(&Qs[sr + RS_RP * it][sn]) = qreg[it];
+        }
+        __syncthreads();
+        if (ch + 1 < nch) fetch(n0 + (int64_t)(ch + 1) * RS_KC);
+#pragma unroll
+        for (int ks = 0; ks < RS_KC; ks += 4) {
+            double fa[4], fb[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                fa[m] = Qb[64 * wj + 16 * m + fc][ks + fr];
+                fb[m] = Ps[64 * wi + 16 * m + fc][ks + fr];
+            }
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi)
+                    acc[mi][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mj], fb[mi], acc[mi][mj], 0, 0, 0);
+        }
+    }
+    double* __restrict__ Ct = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (NB * NB);
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        double* Ci = Ct + 64 * wi + 16 * mi + fc;
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) Ci[(64 * wj + 16 * mj + fr + 4 * rg) * NB] = acc[mi][mj][rg];
+    }
+}
+
+// B's lower tile blockIdx.x = the chunk partials summed in ascending chunk order, laid out as
+// the augmented matrix of a preloaded factorisation of order Mz exactly as post_cov_kernel
+// leaves one: column j < Mz holds S[i, j] + noise (i == j) in rows i < Mz, w_j in row Mz (the
+// v row) and 0 below; columns j >= Mz hold 0. blockIdx.y takes 32 of the tile's columns.
+__global__ __launch_bounds__(256) void rows_syrk_reduce_kernel(const double* __restrict__ part, int chunks,
+                                                               double* __restrict__ B, int64_t ldb, int64_t Mz,
+                                                               double noise) {
+    int bi, bj;
+    tri_index(blockIdx.x, bi, bj);
+    const int r = threadIdx.x & (NB - 1), half = threadIdx.x >> 7;
+    const int64_t i = (int64_t)bi * NB + r;
+    const int64_t tstride = (int64_t)gridDim.x * (NB * NB);
+    for (int cc = 32 * (int)blockIdx.y + half; cc < 32 * ((int)blockIdx.y + 1); cc += 2) {
+        const int64_t j = (int64_t)bj * NB + cc;
+        const double* p = part + (int64_t)blockIdx.x * (NB * NB) + cc * NB + r;
+        double s = 0.0;
+        for (int c = 0; c < chunks; ++c) s += p[(int64_t)c * tstride];
+        double o = 0.0;
+        if (j < Mz) o = i < Mz ? (i == j ? s + noise : s) : (i == Mz ? s : 0.0);
+        B[j * ldb + i] = o;
+    }
+}
+
+// Y[k + j ldy] = A[k lda + Np + row0 + j], k < Mz, j < Ms: the riding rows row0 .. row0 + Ms - 1
+// (a_j^T = (L^{-1} K(Z, xs_j))^T) as the Mz x Ms matrix whose columns rows_from_matrix_kernel
+// puts below the second factorisation. 32x32 blocks through LDS: both sides run contiguously.
+__global__ __launch_bounds__(256) void rows_to_matrix_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                             int64_t row0, int64_t Mz, int64_t Ms,
+                                                             double* __restrict__ Y, int64_t ldy) {
+    __shared__ double t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t j0 = (int64_t)blockIdx.x * 32, k0 = (int64_t)blockIdx.y * 32;
+    for (int kk = ty; kk < 32; kk += 8)
+        t[kk][tx] = (k0 + kk < Mz && j0 + tx < Ms) ? A[(k0 + kk) * lda + Np + row0 + j0 + tx] : 0.0;
+    __syncthreads();
+    for (int jj = ty; jj < 32; jj += 8)
+        if (k0 + tx < Mz && j0 + jj < Ms) Y[(j0 + jj) * ldy + k0 + tx] = t[tx][jj];
+}
+
+// mean_j = sum of the partial dots with the v row, var_j += noise * sum of the partial row norms
+// (post_partial_kernel's partials over the rows below the second factorisation, fixed order);
+// var comes in holding k(xs_j, xs_j) - |a_j|^2 from the first evaluation.
+__global__ __launch_bounds__(256) void sparse_post_finish_kernel(const double* __restrict__ pm,
+                                                                 const double* __restrict__ pv, int64_t M, int nk,
+                                                                 double noise, double* __restrict__ mean,
+                                                                 double* __restrict__ var) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    double m = 0.0, v = 0.0;
+    for (int y = 0; y < nk; ++y) {
+        m += pm[(int64_t)y * M + j];
+        v += pv[(int64_t)y * M + j];
+    }
+    mean[j] = m;
+    var[j] = var[j] + noise * v;
+}
+
 // =================================================================================
 // Persistent tail: the last T <= TAIL_TMAX tile columns ts .. nt-1
 // of the factorisation in ONE launch, as a dataflow of tile tasks instead of per-column
@@ -4071,6 +4247,44 @@ void launch_mirror_lower(hipStream_t s, double* B, int64_t ldb, int64_t M) {
     if (!guard_launch("mirror_lower_kernel", B, 0, (M - 1) * ldb + M, 1)) return;
     const unsigned nb = (unsigned)((M + 31) / 32);
     mirror_lower_kernel<<<dim3(nb, nb), dim3(256), 0, s>>>(B, ldb, M);
+}
+
+void launch_rows_syrk(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t N, int64_t rows,
+                      const double* y, int64_t chunks, int64_t chunk_rows, double* part, double* B, int64_t ldb,
+                      double noise) {
+    if (Mz <= 0 || N <= 0 || chunks <= 0) return;
+    const int64_t ntb = Np / NB, ntl = ntb * (ntb + 1) / 2;
+    if (guard_launch("sparse_rows_prep_kernel", A, Mz * lda + Np, (Np - 1) * lda + Np + rows))
+        sparse_rows_prep_kernel<<<dim3((unsigned)((rows + 255) / 256), (unsigned)(Np - Mz)), dim3(256), 0, s>>>(
+            A, lda, Np, Mz, N, rows, y);
+    // reads rows n < roundup(N, RS_KC) of every column of A's riding rows; writes B's lower tiles
+    const int64_t nread = (N + RS_KC - 1) / RS_KC * RS_KC;
+    const bool a_ok = guard_launch("rows_syrk_kernel (riding rows)", A, Np, (Np - 1) * lda + Np + nread);
+    const bool b_ok = guard_launch("rows_syrk_reduce_kernel", B, 0, tiles_end(ldb, ntb - 1, ntb - 1), 1);
+    if (!a_ok || !b_ok || nread > rows) return;
+    rows_syrk_kernel<<<dim3((unsigned)ntl, (unsigned)chunks), dim3(256), 0, s>>>(A, lda, Np, N, chunk_rows, part);
+    rows_syrk_reduce_kernel<<<dim3((unsigned)ntl, NB / 32), dim3(256), 0, s>>>(part, (int)chunks, B, ldb, Mz, noise);
+}
+
+void launch_rows_to_matrix(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t row0, int64_t Mz,
+                           int64_t Ms, double* Y, int64_t ldy) {
+    if (Mz <= 0 || Ms <= 0) return;
+    if (!guard_launch("rows_to_matrix_kernel", A, Np + row0, (Mz - 1) * lda + Np + row0 + Ms)) return;
+    rows_to_matrix_kernel<<<dim3((unsigned)((Ms + 31) / 32), (unsigned)((Mz + 31) / 32)), dim3(256), 0, s>>>(
+        A, lda, Np, row0, Mz, Ms, Y, ldy);
+}
+
+void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t Ms, double noise,
+                        double* partial, double* mean, double* var) {
+    if (Mz <= 0 || Ms <= 0) return;
+    if (!guard_launch("post_partial_kernel (sparse)", A, 0, (Mz - 1) * lda + Np + Ms)) return;
+    const int nk = (int)((Mz + 511) / 512);
+    double* pm = partial;
+    double* pv = partial + (size_t)nk * Ms;
+    post_partial_kernel<<<dim3((unsigned)((Ms + 255) / 256), (unsigned)nk), dim3(256), 0, s>>>(A, lda, Np, Mz, Ms, pm,
+                                                                                             pv);
+    sparse_post_finish_kernel<<<dim3((unsigned)((Ms + 255) / 256)), dim3(256), 0, s>>>(pm, pv, Ms, nk, noise, mean,
+                                                                                      var);
 }
 
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean) {

@@ -271,6 +271,55 @@ int gaplac_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double*
                             int64_t R, const double* Ys, int64_t ldys,
                             double* out_logpdf, double* out_logdet, double* out_quad);
 
+/* Inducing-point (VFE, Titsias) approximation: Mz inducing inputs Z (Mz x D column-major, leading
+ * dimension ldz, the same columns as X) stand in for the N training points, so nothing of order
+ * N x N is formed. jitter >= 0 is the variance of f(z, jitter). Terms, groups and NOISE terms mean
+ * what they mean for gaplac_posterior_mean_var with (Z, jitter) as the training set and the rows
+ * of X, then Xs, as its test points (cross-covariances use the latent kernel; a NOISE term is 0
+ * across point sets and counts in the kernel diagonal). With Kuu + jitter I = L L^T,
+ * V^T = K(X, Z) L^{-T} (N x Mz), a_j = L^{-1} K(Z, xs_j), S = noise I + (V^T)^T V^T = L_S L_S^T,
+ * w = (V^T)^T y and u = L_S^{-1} w:
+ *     trace  = sum_n ( k(x_n, x_n) - |V^T[n, :]|^2 )
+ *     logdet = (N - Mz) log noise + 2 sum_i log (L_S)_ii
+ *     quad   = ( y^T y - |u|^2 ) / noise
+ *     dtc    = -( N log 2pi + logdet + quad ) / 2      = log N(y | 0, Q + noise I),
+ *                                                         Q = K(X, Z) (Kuu + jitter I)^{-1} K(Z, X)
+ *     elbo   = dtc - trace / (2 noise)
+ *     mean_j = (L_S^{-1} a_j) . u
+ *     var_j  = k(xs_j, xs_j) - |a_j|^2 + noise |L_S^{-1} a_j|^2
+ * One factorisation of order Mz with the N (+ Ms) points riding as extra rows, one fp64-MFMA
+ * product for S split over N into chunks summed in a fixed order (the split depends on (N, Mz)
+ * alone: a call is bitwise repeatable), and a second factorisation of order Mz.
+ * Common convention: every output is NaN-filled first; info > 0 when either Cholesky fails (all
+ * outputs stay NaN; gaplac_last_error names the matrix: the inducing covariance, or S).
+ * GAPLAC_E_PARAM for noise <= 0 or non-finite, jitter < 0 or non-finite; GAPLAC_E_ARG for
+ * Mz < 0, Ms < 0, a leading dimension below its row count, a NULL matrix of positive size,
+ * out_elbo NULL; GAPLAC_E_OOM when the workspaces do not fit or ceil((N + Ms)/128) > 65535 (no
+ * chunking). N = 0: elbo = dtc = 0 (trace, logdet, quad 0) and the posterior is the prior (mean 0,
+ * variance k(xs_j, xs_j)). Mz = 0: Q = 0 (dtc = log N(y | 0, noise I), trace = sum_n k(x_n, x_n),
+ * the posterior is the prior). Ms = 0: 0 after the argument and term checks, nothing written.
+ * The context stays usable after every failure.
+ *
+ * elbo: every output except out_elbo may be NULL.
+ * Replaces: elbo(VFE(f(z, jitter)), f(x, noise), y) and dtc(...) of AbstractGPs 0.5.12 (out_dtc). */
+int gaplac_sparse_elbo(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                       int32_t T, const gaplac_term* terms, double noise, const double* y,
+                       int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                       double* out_elbo, double* out_dtc, double* out_trace, double* out_logdet,
+                       double* out_quad);
+/* The approximate posterior at Ms test points Xs (Ms x D column-major, leading dimension ldxs);
+ * out_mean / out_var have Ms entries; either may be NULL.
+ * Replaces: mean_and_var(posterior(VFE(f(z, jitter)), f(x, noise), y), xs) of AbstractGPs 0.5.12. */
+int gaplac_sparse_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                                     int32_t T, const gaplac_term* terms, double noise, const double* y,
+                                     int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                                     int64_t Ms, const double* Xs, int64_t ldxs,
+                                     double* out_mean, double* out_var);
+/* Host-only: the split of the product for S over the N rows, *out_chunks chunks of
+ * *out_chunk_rows rows (the last one ragged), summed in ascending order. A function of (N, Mz)
+ * alone. GAPLAC_E_ARG for N < 0, Mz < 0 or a NULL output. Not in the reference. */
+int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows);
+
 /* Debug / parity entries (tests only; not on the timed path). */
 /* Gram matrix sum_t K_t(X) + noise*I as a dense N×N column-major host matrix
  * (replaces KernelFunctions.kernelmatrix + Diagonal(Fill(noise, N))). */
@@ -355,6 +404,14 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
  * (the negative controls); 0: as allocated. Not in the reference. */
 int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_t short_ws,
                             int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for the sparse entries: the posterior evaluation of order Mz with N + Ms riding
+ * rows, the launches that form S (and, with Ms > 0, the transposing copy of the test points'
+ * rows) against both workspaces, and the second factorisation of order Mz (Ms > 0: with Ms riding
+ * rows and their reduction, as gaplac_sparse_posterior_mean_var; Ms = 0: plain, as
+ * gaplac_sparse_elbo). short_ws 1 / 2: the first / second workspace one element short (the
+ * negative controls); 0: as allocated. Not in the reference. */
+int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws,
+                             int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* Host-only accounting of the single-GPU schedule for order N (GAPLAC_SPW = spw,
  * GAPLAC_PAIR_DEPTH = depth (0: auto), band extension pair_ext (0/1), GAPLAC_PAIR_M =
  * pair_m): every tile column gets every earlier panel column exactly once, in order, before

@@ -9,6 +9,9 @@
 //   gaplac_plan_check_joint    - the joint posterior's three stages (the posterior evaluation,
 //                                the covariance launches against both workspaces, the
 //                                preloaded factorisation of order M, plain or with riding rows);
+//   gaplac_plan_check_sparse   - the sparse entries' three stages (the posterior evaluation of
+//                                order Mz with N + Ms riding rows, the launches that form S, the
+//                                preloaded factorisation of order Mz) and gaplac_sparse_split;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -89,6 +92,28 @@ int main() {
                        (long long)N, (long long)R);
             }
     EXPECT(gaplac_plan_check_joint(10, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "joint: M = 0 accepted");
+    // the sparse entries: stages 1-3 (Ms = 0: elbo; Ms > 0: the posterior), the split rule, then
+    // each workspace one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t Mz : {1, 5, 127, 128, 129, 257, 513, 1024, 4096})
+            for (int64_t Ms : {0, 1, 129, 1000})
+                for (int64_t N : {1, 5, 127, 128, 129, 300, 1023, 1024, 1025, 2051, 16384, 70000}) {
+                    const int rc = gaplac_plan_check_sparse(N, Mz, Ms, spw, 0, &a, &b, msg, sizeof msg);
+                    EXPECT(rc == 0 && a > 0 && b == 0, "plan_check_sparse N=%lld Mz=%lld Ms=%lld spw=%d: rc %d violations %lld %s",
+                           (long long)N, (long long)Mz, (long long)Ms, spw, rc, (long long)b, msg);
+                    int64_t chunks = 0, rows = 0;
+                    EXPECT(gaplac_sparse_split(N, Mz, &chunks, &rows) == 0 && rows > 0 && chunks == (N + rows - 1) / rows,
+                           "sparse_split N=%lld Mz=%lld", (long long)N, (long long)Mz);
+                    ++checks;
+                }
+    for (int short_ws : {1, 2})
+        for (int64_t N : {1, 128, 300, 4096})
+            for (int64_t Ms : {0, 5}) {
+                const int rc = gaplac_plan_check_sparse(N, 129, Ms, 4, short_ws, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && b >= 1, "negative control (sparse, short_ws %d) N=%lld Ms=%lld not reported", short_ws,
+                       (long long)N, (long long)Ms);
+            }
+    EXPECT(gaplac_plan_check_sparse(10, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "sparse: Mz = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
