@@ -23,6 +23,69 @@
 
 using namespace gaplac;
 
+namespace gaplac {
+// What one evaluation carries besides its matrix: the rows that ride below it, factored along
+// (lda = Np + 128 tiles), and the two flags that describe the same evaluation. A value: an entry
+// builds one with a named constructor and passes it to eval_device, whose EvalScope installs it
+// in the context for that call and puts "none" back on every way out. Nothing else writes it.
+//   mode 1 = identity rows E = [I 0] -> L^{-T} (gradient, gaplac_logpdf_grad)
+//   mode 2 = K(xs, X) -> (L^{-1} K(X, xs))^T (posterior, gaplac_posterior_mean_var, §10)
+//   mode 3 = Y^T -> (L^{-1} Y)^T (the responses of gaplac_logpdf_multi, §10.5)
+// Modes 2 and 3 are dense rows (dense_rows): one schedule for both.
+struct ExtraRows {
+    int mode = 0;   // 0: none
+    int tiles = 0;  // tile rows
+    int64_t M = 0;  // mode 2: test points; mode 3: responses R
+    // mode 2, gaplac_posterior_components (§10.7): the M = G * Mc rows are packed components,
+    // built and finished per row by the selector; everything between sees M ordinary rows
+    bool comp = false;
+    CompSel sel{};
+    // mode 3: the responses on the device, ld ldy, and N values subtracted from every response
+    // (or nullptr)
+    const double* Y = nullptr;
+    int64_t ldy = 0;
+    const double* sub = nullptr;
+    bool prebuilt = false;    // the matrix is already in the workspace: no Gram launch (§10.6)
+    bool singletons = true;   // mode 1: single-term product groups only (the fused path's case)
+
+    static ExtraRows dense(int mode, int64_t n) {  // n rows in ceil(n / 128) tile rows
+        ExtraRows x;
+        x.mode = mode;
+        x.tiles = (int)((n + NB - 1) / NB);
+        x.M = n;
+        return x;
+    }
+    // identity rows for order N: one tile row per tile column of the augmented matrix
+    static ExtraRows identity(int64_t N, bool singletons = true) {
+        ExtraRows x;
+        x.mode = 1;
+        x.tiles = (int)((N + NB) / NB);
+        x.singletons = singletons;
+        return x;
+    }
+    static ExtraRows test_points(int64_t M) { return dense(2, M); }
+    static ExtraRows components(const CompSel& sel) {  // G * Mc packed rows
+        ExtraRows x = dense(2, (int64_t)sel.G * sel.Mc);
+        x.comp = true;
+        x.sel = sel;
+        return x;
+    }
+    static ExtraRows responses(int64_t R, const double* Y, int64_t ldy, const double* sub = nullptr) {
+        ExtraRows x = dense(3, R);
+        x.Y = Y;
+        x.ldy = ldy;
+        x.sub = sub;
+        return x;
+    }
+    // the same rows on a matrix the caller has already put in the workspace
+    ExtraRows on_prebuilt() const {
+        ExtraRows x = *this;
+        x.prebuilt = true;
+        return x;
+    }
+};
+}  // namespace gaplac
+
 struct gaplac_ctx {
     int device = 0;
     hipStream_t s_main = nullptr, s_panel = nullptr;
@@ -75,7 +138,6 @@ struct gaplac_ctx {
     int pair_ext = 1;     // 1 = a deferring step also updates the band after next (§3.2)
     int band_tiles_m = 64;  // GAPLAC_BAND_TILES_M: bands of >= this many tile rows as whole tiles
     int grad_fused = 1;     // GAPLAC_GRAD_FUSED: -C^{-1} contracted inside cinv_contract_kernel (0: stored, then contracted)
-    bool grad_singletons = true;  // the gradient's formula has single-term groups only (the fused path's case)
     int la_tiles_m = 120;   // the lookahead of >= this many tile rows as whole tiles (0: never)
     // GAPLAC_TAIL_SIM: the single-evaluation tail list ordered by a simulated schedule
     // (sim_order_tail_tasks); -1 = for tails of fewer than 80 tile columns (measured: T = 33
@@ -150,22 +212,11 @@ struct gaplac_ctx {
         int m0 = 0, B = 0;                                // its models
     } bw[2];  // two sets: one launch's Grams overlap the previous launch's tail
     bool borrowed_inputs = false;  // dX / dv belong to the parent
-    // Extra rows below the matrix, factored along (lda = Np + 128 xr_tiles):
-    //   1 = identity rows E = [I 0] -> L^{-T} (gradient, gaplac_logpdf_grad)
-    //   2 = K(xs, X) -> (L^{-1} K(X, xs))^T (posterior, gaplac_posterior_mean_var, §10)
-    //   3 = Y^T -> (L^{-1} Y)^T (the responses of gaplac_logpdf_multi, §10.5)
-    // Modes 2 and 3 are dense rows (dense_rows): one schedule for both.
-    int xr_mode = 0;
-    int xr_tiles = 0;
-    int64_t xr_M = 0;       // mode 2: test points; mode 3: responses R
-    double* dXs = nullptr;  // mode 2: test inputs (ld M; per-component rows: ld xr_sel.Mc)
-    // mode 2, gaplac_posterior_components (§10.7): the xr_M = G * Mc rows are packed components,
-    // built and finished per row by the selector; everything between sees xr_M ordinary rows
-    bool xr_comp = false;
-    CompSel xr_sel{};
+    // The evaluation in flight (none between evaluations): written by EvalScope alone, read by
+    // the engine (factor_and_reduce, tail_allowed, ensure_workspace, enqueue_eval_body, ...)
+    ExtraRows xr;
+    double* dXs = nullptr;  // mode 2: test inputs (ld xr.M; per-component rows: ld xr.sel.Mc)
     size_t dXs_elems = 0;
-    const double* xr_Y = nullptr;  // mode 3: the responses on the device (dY, or the caller's matrix), ld xr_ldy
-    int64_t xr_ldy = 0;
     double* dY = nullptr;  // gaplac_logpdf_multi: the host matrix's copy (ld N)
     size_t dY_elems = 0;
     double* mres = nullptr;  // mode 3 results: quad[R], then logpdf[R]
@@ -179,12 +230,10 @@ struct gaplac_ctx {
     double* pvar = nullptr;
     size_t pmv_elems = 0;
     // Joint posterior: the order-M workspace that post_cov_kernel fills and the
-    // second factorisation runs in. For that factorisation A and B change places and preloaded
-    // is set: the evaluation finds its matrix already built (no Gram launch).
+    // second factorisation runs in. For that factorisation A and B change places (WsSwap) and
+    // the evaluation is described as on_prebuilt(): it finds its matrix already built.
     double* B = nullptr;
     size_t B_elems = 0;
-    bool preloaded = false;
-    const double* xr_sub = nullptr;  // mode 3: N values subtracted from every response (or nullptr)
     // Inducing-point approximation: y on the device and the chunk partials of S
     double* sp_y = nullptr;
     size_t sp_y_elems = 0;
@@ -530,7 +579,7 @@ int factor_superpanel(gaplac_ctx* ctx, hipStream_t sp, int64_t N, int64_t lda, i
     return 0;
 }
 
-// Extra rows, tile rows nt .. nt + xr_tiles - 1 of the column storage,
+// Extra rows, tile rows nt .. nt + xr.tiles - 1 of the column storage,
 // factored along on s_main, off the critical path: once SP p's columns are final (P(p)),
 // its extra-row tiles get the column-by-column substitution (the earlier columns of the SP
 // applied first, K = 128), then SP p is applied to every later column (K = 128 W).
@@ -543,8 +592,8 @@ constexpr int XR_TILE_MIN = 128;
 
 static void extra_rows_chain(gaplac_ctx* ctx, hipStream_t sm, int64_t lda, int nt, int c0, int c1) {
     const int W = ctx->spw;
-    const bool tri = ctx->xr_mode == 1;
-    const int mt = ctx->xr_tiles;
+    const bool tri = ctx->xr.mode == 1;
+    const int mt = ctx->xr.tiles;
     for (int c = c0; c < c1; ++c) {
         double* Acol = ctx->A + (int64_t)c * NB * lda;
         if (c > c0) {
@@ -564,7 +613,7 @@ static void extra_rows_chain(gaplac_ctx* ctx, hipStream_t sm, int64_t lda, int n
 static void extra_rows_update(gaplac_ctx* ctx, hipStream_t sm, int64_t lda, int nt, int c0, int c1, int jb,
                               int je) {
     if (je <= jb) return;
-    const int rows = ctx->xr_mode == 1 ? c1 : ctx->xr_tiles;
+    const int rows = ctx->xr.mode == 1 ? c1 : ctx->xr.tiles;
     BulkArgs ba{ctx->A, lda, Panel{ctx->A + (int64_t)c0 * NB * lda, lda, 0}, nullptr, rows * (je - jb),
                 (c1 - c0) * NB, nt, jb, ColMap{1, 0, ctx->spw}};
     ba.rect_rows = rows;
@@ -582,11 +631,11 @@ static void extra_rows_update(gaplac_ctx* ctx, hipStream_t sm, int64_t lda, int 
 // gradient's identity rows (one per column) never do.
 // Dense extra rows (the posterior's cross-covariance rows, the responses of logpdf_multi):
 // every row of every column is nonzero, so both take the same schedule.
-static bool dense_rows(const gaplac_ctx* ctx) { return ctx->xr_mode == 2 || ctx->xr_mode == 3; }
+static bool dense_rows(const gaplac_ctx* ctx) { return ctx->xr.mode == 2 || ctx->xr.mode == 3; }
 
 static bool tail_allowed(const gaplac_ctx* ctx) {
-    return ctx->xr_mode == 0 || (dense_rows(ctx) && ctx->tailk && ctx->tail_s > 0 &&
-                                 ctx->xr_tiles + std::min(ctx->tail_s, TAIL_TMAX) <= TAIL_TMAX);
+    return ctx->xr.mode == 0 || (dense_rows(ctx) && ctx->tailk && ctx->tail_s > 0 &&
+                                 ctx->xr.tiles + std::min(ctx->tail_s, TAIL_TMAX) <= TAIL_TMAX);
 }
 
 static bool whole_in_tail(const gaplac_ctx* ctx, int nt) {
@@ -602,7 +651,7 @@ static bool whole_in_tail(const gaplac_ctx* ctx, int nt) {
 #define GAPLAC_TAIL_GRAM 1
 #endif
 static bool gram_in_tail(const gaplac_ctx* ctx, int nt, int64_t lda) {
-    return GAPLAC_TAIL_GRAM && ctx->xr_mode == 0 && !ctx->preloaded && whole_in_tail(ctx, nt) &&
+    return GAPLAC_TAIL_GRAM && ctx->xr.mode == 0 && !ctx->xr.prebuilt && whole_in_tail(ctx, nt) &&
            ((int64_t)(NB - 1) * lda + NB) * 8 < ((int64_t)1 << 31);
 }
 
@@ -610,7 +659,7 @@ static bool gram_in_tail(const gaplac_ctx* ctx, int nt, int64_t lda) {
 // (init_result_ctl_kernel, when the Gram is inside the tail) instead of a copy.
 static bool tp_by_init(const gaplac_ctx* ctx, int64_t N) {
     const int64_t Np = round_up(N + 1, NB);
-    return gram_in_tail(ctx, (int)(Np / NB), Np + (int64_t)NB * ctx->xr_tiles);
+    return gram_in_tail(ctx, (int)(Np / NB), Np + (int64_t)NB * ctx->xr.tiles);
 }
 
 static std::vector<int> superpanel_starts(const gaplac_ctx* ctx, int nt) {
@@ -662,7 +711,7 @@ static bool pair_defer(const gaplac_ctx* ctx, const std::vector<int>& spc, int n
     const int jb = p + 2 <= nsp ? spc[(size_t)p + 2] : spc[(size_t)nsp];
     const int je = p + 3 <= nsp ? spc[(size_t)p + 3] : spc[(size_t)nsp];
     return ctx->pair_m > 0 && (pend < 0 || p - pend + 1 < deferral_depth(ctx, nt)) && !ctx->serial &&
-           !ctx->xr_mode && je > jb && p + 1 + ctx->pair_ext < nsp && p + 3 + ctx->pair_ext <= nsp &&
+           !ctx->xr.mode && je > jb && p + 1 + ctx->pair_ext < nsp && p + 3 + ctx->pair_ext <= nsp &&
            nt - spc[(size_t)p + 3 + ctx->pair_ext] >= ctx->pair_m;
 }
 
@@ -708,7 +757,7 @@ constexpr int SPLIT_REST_MIN = 16;
 #endif
 static bool split_wanted(const gaplac_ctx* ctx, int nt) {
     const std::vector<int> spc = superpanel_starts(ctx, nt);  // (a short super-panel phase: not worth it)
-    return GAPLAC_SPLIT && ctx->xr_mode == 0 && !ctx->serial && deferral_depth(ctx, nt) <= GAPLAC_SPLIT_DEPTH &&
+    return GAPLAC_SPLIT && ctx->xr.mode == 0 && !ctx->serial && deferral_depth(ctx, nt) <= GAPLAC_SPLIT_DEPTH &&
            !whole_in_tail(ctx, nt) && spc.back() >= GAPLAC_SPLIT_MINCOLS;
 }
 static bool split_bulk(const gaplac_ctx* ctx, int nt) {
@@ -752,14 +801,14 @@ BulkArgs band_args(const gaplac_ctx* ctx, int64_t lda, int nt, int b0, const Pan
 // kind 5) are event-timed, for the bulk phase's union of launch intervals
 int band_launch(gaplac_ctx* ctx, hipStream_t st, int64_t lda, int nt, int b0, const Panel& pn, int kdep, bool whole) {
     const BulkArgs bb = band_args(ctx, lda, nt, b0, pn, kdep, whole);
-    return timed_launch(ctx, ctx->prof_mode == 2 && whole && !ctx->xr_mode, st,
+    return timed_launch(ctx, ctx->prof_mode == 2 && whole && !ctx->xr.mode, st,
                         {0, band_flops(nt - b0, ctx->spw, kdep), 0.0, 5},
                         [&] { launch_bulk(st, bb, slot(ctx, 5, 0)); });
 }
 
 // s_main waits for what the extra rows' streams hold (gradient / posterior, not serial)
 int join_extra_streams(gaplac_ctx* ctx, hipStream_t sm) {
-    if (!ctx->xr_mode || ctx->serial) return 0;
+    if (!ctx->xr.mode || ctx->serial) return 0;
     for (hipStream_t sx : {ctx->s_extra, ctx->s_xrest}) {
         HIPQ(ctx, hipEventRecord(ctx->ev_xdone, sx));
         HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
@@ -843,7 +892,7 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
             const Panel pn{ctx->A + (int64_t)c0 * NB * lda, lda, 0};
             if (GAPLAC_CHAIN_SKIP >= 2 && !ctx->dry) {
             } else if (ctx->la_tiles_m > 0 && mla >= ctx->la_tiles_m && c2 - c1 == W && ctx->band_off.size() > (size_t)mla &&
-                       !ctx->xr_mode) {
+                       !ctx->xr.mode) {
                 // the lookahead as whole 128x128 tiles (the band list of SP p+1's columns):
                 // less CU time than the quadrant kernel while the trailing matrix is large
                 if ((frc = band_launch(ctx, sp, lda, nt, c1, pn, kd, true))) return frc;
@@ -902,7 +951,7 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
             if ((frc = bulk_tri(jb, Panel{ctx->A + (int64_t)c0 * NB * lda, lda, 0}, kd))) return frc;
             HIPQ(ctx, hipEventRecord(ctx->ev_R[p & 1], sm));
         }
-        if (ctx->xr_mode) {
+        if (ctx->xr.mode) {
             // extra rows: they only need SP p final (P(p)) and touch rows no other stream
             // writes. s_extra takes SP p's column chain and then its update of SP p+1's
             // columns; the update of the columns after those (the bulk of the K = 128 W work)
@@ -934,8 +983,8 @@ int factor_and_reduce(gaplac_ctx* ctx, int64_t N, int64_t lda, int nt) {
     if (spc[(size_t)nsp] < nt) {
         const int ts = spc[(size_t)nsp], T = nt - ts;
         // dense extra rows: factored along inside the tail
-        const int X = dense_rows(ctx) ? ctx->xr_tiles : 0;
-        if (ctx->tailk && T + X <= TAIL_TMAX && (ctx->xr_mode == 0 || X > 0)) {
+        const int X = dense_rows(ctx) ? ctx->xr.tiles : 0;
+        if (ctx->tailk && T + X <= TAIL_TMAX && (ctx->xr.mode == 0 || X > 0)) {
             // the tail as one persistent dataflow launch
             // the extra rows' super-panel updates of the tail's columns land first
             if ((frc = join_extra_streams(ctx, sm))) return frc;
@@ -1035,7 +1084,7 @@ int ensure_tile_lists(gaplac_ctx* ctx, int nt) {
 // reduction, result copy to the pinned host record. Inputs: ctx->dX (ld N), ctx->dv,
 // ctx->dtp.
 int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt) {
-    const int64_t lda = Np + (int64_t)NB * ctx->xr_tiles;
+    const int64_t lda = Np + (int64_t)NB * ctx->xr.tiles;
     const bool gram_tail = gram_in_tail(ctx, nt, lda);
     if (gram_tail && !ctx->tctl && !ctx->dry) HIPCK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->tctl), sizeof(TailCtl)));
     if (gram_tail)  // the tail's counters zeroed here (factor_and_reduce then skips its memset)
@@ -1050,7 +1099,7 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     const double bpt = 8.0 * NB * NB;  // bytes per tile
     const double b1 = bpt * (tri(nt) - tri(std::max(0, nt - ctx->spw))) + 8.0 * (double)N * (D + 1);
     const double b2 = bpt * tri(std::max(0, nt - ctx->spw));
-    if (ctx->preloaded) {
+    if (ctx->xr.prebuilt) {
         // the matrix is already in the workspace (post_cov_kernel, earlier on s_main): the panel
         // stream's two waits for the Gram hold behind it
         HIPQ(ctx, hipEventRecord(ctx->ev_gram, ctx->s_main));
@@ -1062,34 +1111,34 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
                           slot(ctx, 1, b2));
         HIPQ(ctx, hipEventRecord(ctx->ev_gram2, ctx->s_main));
     }
-    if (ctx->xr_mode == 1) launch_init_identity_rows(ctx->s_main, ctx->A, lda, Np, nt, ctx->spw);
-    if (ctx->xr_mode == 2)
-        launch_cross_gram(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->dX, N, ctx->dXs,
-                          ctx->xr_comp ? ctx->xr_sel.Mc : ctx->xr_M, ctx->dtp, ctx->xr_comp ? &ctx->xr_sel : nullptr);
-    if (ctx->xr_mode == 3)
-        launch_rows_from_matrix(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr_M, ctx->xr_tiles, ctx->xr_Y,
-                                ctx->xr_ldy, ctx->xr_sub);
-    if (ctx->xr_mode && !ctx->serial) {  // the extra-row stream starts after their init
+    if (ctx->xr.mode == 1) launch_init_identity_rows(ctx->s_main, ctx->A, lda, Np, nt, ctx->spw);
+    if (ctx->xr.mode == 2)
+        launch_cross_gram(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr.M, ctx->xr.tiles, ctx->dX, N, ctx->dXs,
+                          ctx->xr.comp ? ctx->xr.sel.Mc : ctx->xr.M, ctx->dtp, ctx->xr.comp ? &ctx->xr.sel : nullptr);
+    if (ctx->xr.mode == 3)
+        launch_rows_from_matrix(ctx->s_main, ctx->A, lda, Np, nt, N, ctx->xr.M, ctx->xr.tiles, ctx->xr.Y,
+                                ctx->xr.ldy, ctx->xr.sub);
+    if (ctx->xr.mode && !ctx->serial) {  // the extra-row stream starts after their init
         HIPQ(ctx, hipEventRecord(ctx->ev_xinit, ctx->s_main));
         HIPQ(ctx, hipStreamWaitEvent(ctx->s_extra, ctx->ev_xinit, 0));
     }
     int rc;
     if ((rc = factor_and_reduce(ctx, N, lda, nt))) return rc;
-    if (ctx->xr_mode == 2)
-        launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dXs,
-                         ctx->xr_comp ? ctx->xr_sel.Mc : ctx->xr_M, ctx->dtp, ctx->gpart, ctx->pmean, ctx->pvar,
-                         ctx->xr_comp ? &ctx->xr_sel : nullptr);
-    if (ctx->xr_mode == 3)
-        launch_quad_rows(ctx->s_main, ctx->A, lda, Np, N, ctx->xr_M, ctx->dres, ctx->gpart, ctx->mres,
-                         ctx->mres ? ctx->mres + ctx->xr_M : nullptr /* (a dry walk has no buffers) */);
-    if (ctx->xr_mode == 1) {
+    if (ctx->xr.mode == 2)
+        launch_posterior(ctx->s_main, ctx->A, lda, Np, N, ctx->xr.M, ctx->dXs,
+                         ctx->xr.comp ? ctx->xr.sel.Mc : ctx->xr.M, ctx->dtp, ctx->gpart, ctx->pmean, ctx->pvar,
+                         ctx->xr.comp ? &ctx->xr.sel : nullptr);
+    if (ctx->xr.mode == 3)
+        launch_quad_rows(ctx->s_main, ctx->A, lda, Np, N, ctx->xr.M, ctx->dres, ctx->gpart, ctx->mres,
+                         ctx->mres ? ctx->mres + ctx->xr.M : nullptr /* (a dry walk has no buffers) */);
+    if (ctx->xr.mode == 1) {
         // Fused (single-term groups): alpha = Y z first (HBM-bound, ~0.2 ms alone), then M =
         // -C^{-1} tile by tile contracted in place with every dC/dtheta (cinv_contract_kernel:
         // the tile is never stored nor read back), all on s_main.
         // Else (or GAPLAC_GRAD_FUSED=0): alpha on s_extra beside M over the factor storage on
         // s_main (both only read Y; z is copied out first, cinv may overwrite row N), then the
         // contraction on s_main once alpha is in. Both end in the fixed-order reduction.
-        const bool fused = ctx->grad_fused && ctx->grad_singletons;
+        const bool fused = ctx->grad_fused && ctx->xr.singletons;
         hipStream_t sm = ctx->s_main;
         hipStream_t sx = fused || ctx->serial ? sm : ctx->s_extra;  // alpha's stream
         const int m = (int)((N + NB - 1) / NB);
@@ -1172,12 +1221,12 @@ int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
     const int nt = (int)(Np / NB);
     int rc;
     HIPCK(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure(ctx, &ctx->A, &ctx->A_elems, (size_t)(Np + (int64_t)NB * ctx->xr_tiles) * Np))) return rc;
+    if ((rc = ensure(ctx, &ctx->A, &ctx->A_elems, (size_t)(Np + (int64_t)NB * ctx->xr.tiles) * Np))) return rc;
     // the extra rows take both optional streams; the split bulk updates of a plain evaluation
     // (factor_and_reduce) take s_xrest, which would idle there
-    if ((rc = ensure_streams(ctx, ctx->xr_mode != 0, ctx->xr_mode != 0 || split_wanted(ctx, nt)))) return rc;
-    if (ctx->xr_mode == 2) {
-        const size_t M = (size_t)ctx->xr_M;
+    if ((rc = ensure_streams(ctx, ctx->xr.mode != 0, ctx->xr.mode != 0 || split_wanted(ctx, nt)))) return rc;
+    if (ctx->xr.mode == 2) {
+        const size_t M = (size_t)ctx->xr.M;
         if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, 2 * M * (size_t)((N + 511) / 512)))) return rc;
         if (ctx->pmv_elems < M) {
             if (ctx->pmean) (void)hipFree(ctx->pmean);
@@ -1190,12 +1239,12 @@ int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
             ctx->pmv_elems = M;
         }
     }
-    if (ctx->xr_mode == 3) {
-        const size_t R = (size_t)ctx->xr_M;
+    if (ctx->xr.mode == 3) {
+        const size_t R = (size_t)ctx->xr.M;
         if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, R * (size_t)((N + 511) / 512)))) return rc;
         if ((rc = ensure(ctx, &ctx->mres, &ctx->mres_elems, 2 * R))) return rc;
     }
-    if (ctx->xr_mode == 1) {
+    if (ctx->xr.mode == 1) {
         const int m = (int)((N + NB - 1) / NB);
         const size_t nk = (size_t)((N + 511) / 512);
         const size_t part = std::max(nk * (size_t)N, (size_t)m * (m + 1) / 2 * (GAPLAC_MAX_TERMS + 1));
@@ -1216,8 +1265,17 @@ int ensure_workspace(gaplac_ctx* ctx, int64_t N) {
     return ensure_tile_lists(ctx, nt);
 }
 
+// The one writer of ctx->xr: the description holds for as long as this lives (one evaluation's
+// enqueue, or one dry walk) and "none" is back on every way out.
+struct EvalScope {
+    gaplac_ctx* c;
+    EvalScope(gaplac_ctx* ctx, const ExtraRows& xr) : c(ctx) { c->xr = xr; }
+    ~EvalScope() { c->xr = ExtraRows{}; }
+};
+
 // Eager enqueue of one evaluation (no profiling, no wait): the batch lanes.
 int eval_enqueue(gaplac_ctx* ctx, int64_t N, int32_t D, const TermPack& tp) {
+    EvalScope scope(ctx, ExtraRows{});
     int rc;
     if ((rc = ensure_workspace(ctx, N))) return rc;
     const int64_t Np = round_up(N + 1, NB);
@@ -1236,9 +1294,10 @@ int eval_wait(gaplac_ctx* ctx, EvalResult* out) {
     return 0;
 }
 
-// Full evaluation; inputs already in ctx->dX (ld N) / ctx->dv, term pack in tp (host).
-// Leaves the factor in ctx->A.
-int eval_device(gaplac_ctx* ctx, int64_t N, int32_t D, const TermPack& tp, EvalResult* out) {
+// Full evaluation; inputs already in ctx->dX (ld N) / ctx->dv, term pack in tp (host), the
+// riding rows (and whether the matrix is prebuilt) in xr. Leaves the factor in ctx->A.
+int eval_device(gaplac_ctx* ctx, int64_t N, int32_t D, const TermPack& tp, const ExtraRows& xr, EvalResult* out) {
+    EvalScope scope(ctx, xr);
     const int64_t Np = round_up(N + 1, NB);
     const int nt = (int)(Np / NB);
     int rc;
@@ -1327,6 +1386,84 @@ void nan_out(double* a, double* b, double* c) {
     if (c) *c = NAN;
 }
 
+// Test inputs into ctx->dXs (ld rows): rows [r0, r0 + m) from the host block Xs (ld ldxs).
+int upload_test_inputs(gaplac_ctx* ctx, int32_t D, int64_t rows, int64_t r0, int64_t m, const double* Xs,
+                       int64_t ldxs) {
+    int rc;
+    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, (size_t)rows * (size_t)(D > 0 ? D : 1)))) return rc;
+    if (D > 0 && m > 0)
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs + r0, (size_t)rows * 8, Xs, (size_t)ldxs * 8, (size_t)m * 8, (size_t)D,
+                                    hipMemcpyHostToDevice, ctx->s_main));
+    return 0;
+}
+
+// Launches outside an evaluation, under a footprint guard over ctx->A (with_B: and ctx->B as its
+// second region): a launch whose grid would leave them is not enqueued and the entry fails.
+template <typename Launches>
+int guarded(gaplac_ctx* ctx, bool with_B, Launches&& launches) {
+    LaunchGuard g;
+    g.base = ctx->A;
+    g.elems = (int64_t)ctx->A_elems;
+    if (with_B) {
+        g.base2 = ctx->B;
+        g.elems2 = (int64_t)ctx->B_elems;
+    }
+    {
+        GuardScope scope(&g);
+        launches();
+    }
+    if (g.violations)
+        return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
+    HIPCK(ctx, hipGetLastError());
+    return 0;
+}
+
+// Diagnostics (GAPLAC_TAIL_TRACE): `stage` on s_main between two hipEvents, "a b ms" of it alone
+// appended to <trace path><ext>; without a trace path, `stage` and nothing else.
+template <typename Stage>
+int trace_timed(gaplac_ctx* ctx, const char* ext, int64_t a, int64_t b, Stage&& stage) {
+    if (ctx->ttrace_path.empty()) return stage();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Owner {  // the events end with this call, whichever way it returns
+        hipEvent_t* e;
+        ~Owner() {
+            for (int i = 0; i < 2; ++i)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } owner{ev};
+    HIPCK(ctx, hipEventCreate(&ev[0]));
+    if (hipEventCreate(&ev[1]) != hipSuccess) return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
+    (void)hipEventRecord(ev[0], ctx->s_main);
+    if (int rc = stage()) return rc;
+    float ms = 0.f;
+    const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
+                    hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+    if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ext).c_str(), "a") : nullptr) {
+        std::fprintf(f, "%lld %lld %.6f\n", (long long)a, (long long)b, (double)ms);
+        std::fclose(f);
+    }
+    return 0;
+}
+
+// k(x_j, x_j) of row j of a host matrix (the prior variance; a NOISE term counts). With a
+// selector: of component g alone (a term outside it contributes the factor 0.0).
+double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j, const CompSel* sel = nullptr,
+                  int32_t g = 0) {
+    double kd = 0.0, pr = 1.0;
+    for (int t = 0; t < tp.T; ++t) {
+        const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + j];
+        double k = 1.0;
+        if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
+        if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
+        pr *= !sel || sel->comp[t] == g ? k : 0.0;
+        if (tp.last_in_group[t]) {
+            kd += pr;
+            pr = 1.0;
+        }
+    }
+    return kd;
+}
+
 // Shared body of gaplac_logpdf / _device.
 int logpdf_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                 const gaplac_term* terms, double noise, const double* v, double* out_logpdf, double* out_logdet,
@@ -1346,7 +1483,7 @@ int logpdf_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const dou
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, v, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}, &r))) return rc;
     return finish(r, out_logpdf, out_logdet, out_quad);
 }
 
@@ -1379,20 +1516,15 @@ int logpdf_grad_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, cons
         gp.gstart[t] = a;
         gp.gend[t] = b;
     }
-    ctx->grad_singletons = true;
-    for (int t = 0; t < T; ++t) ctx->grad_singletons = ctx->grad_singletons && gp.gend[t] - gp.gstart[t] == 1;
+    bool singletons = true;
+    for (int t = 0; t < T; ++t) singletons = singletons && gp.gend[t] - gp.gstart[t] == 1;
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, v, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     tp.noise = noise;
     *ctx->hgp = gp;
     HIPCK(ctx, hipMemcpyAsync(ctx->dgp, ctx->hgp, sizeof(GradTermPack), hipMemcpyHostToDevice, ctx->s_main));
-    ctx->xr_mode = 1;
-    ctx->xr_tiles = (int)(round_up(N + 1, NB) / NB);
     EvalResult r;
-    rc = eval_device(ctx, N, D, tp, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    if (rc) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows::identity(N, singletons), &r))) return rc;
     rc = finish(r, out_logpdf, nullptr, nullptr);
     if (rc) return rc;  // PosDefException: gradients stay NaN
     if (out_dv) HIPCK(ctx, hipMemcpy(out_dv, ctx->gdv, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
@@ -1420,38 +1552,16 @@ int posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64
     HIPCK(ctx, hipSetDevice(ctx->device));
     if (N == 0) {  // posterior of an empty FiniteGP = the prior: mean 0, var kdiag
         for (int64_t j = 0; j < M; ++j) {
-            double kd = 0.0, pr = 1.0;
-            for (int t = 0; t < T; ++t) {
-                const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : Xs[(int64_t)tp.col[t] * ldxs + j];
-                double k = 1.0;
-                if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
-                if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
-                pr *= k;
-                if (tp.last_in_group[t]) {
-                    kd += pr;
-                    pr = 1.0;
-                }
-            }
             if (out_mean) out_mean[j] = 0.0;
-            if (out_var) out_var[j] = kd;
+            if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
         }
         return 0;
     }
     if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
-    const size_t nxs = (size_t)M * (size_t)(D > 0 ? D : 1);
-    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, nxs))) return rc;
-    if (D > 0)
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)M * 8, Xs, (size_t)ldxs * 8, (size_t)M * 8, (size_t)D,
-                                    hipMemcpyHostToDevice, ctx->s_main));
+    if ((rc = upload_test_inputs(ctx, D, M, 0, M, Xs, ldxs))) return rc;
     tp.noise = noise;
-    ctx->xr_mode = 2;
-    ctx->xr_tiles = (int)((M + NB - 1) / NB);
-    ctx->xr_M = M;
     EvalResult r;
-    rc = eval_device(ctx, N, D, tp, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    if (rc) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows::test_points(M), &r))) return rc;
     rc = finish(r, nullptr, nullptr, nullptr);
     if (rc) return rc;
     if (out_mean) HIPCK(ctx, hipMemcpy(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost));
@@ -1460,7 +1570,7 @@ int posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64
 }
 
 // Body of gaplac_posterior_components: the posterior evaluation with the
-// G components' cross-covariances as G * M packed riding rows (xr_mode 2 with the selector).
+// G components' cross-covariances as G * M packed riding rows (ExtraRows::components).
 int posterior_components_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                               const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
                               int64_t ldxs, int32_t G, const int32_t* comp, double* out_mean, int64_t ldm,
@@ -1494,46 +1604,20 @@ int posterior_components_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
     if (G == 0 || M == 0) return 0;
     if (M > ((int64_t)65535 * NB) / G)  // the cross-covariance grid's tile rows
         return set_err(ctx, GAPLAC_E_OOM, "G * M = %d * %lld rows exceed 65535 tile rows", G, (long long)M);
-    const int64_t R = (int64_t)G * M;
     HIPCK(ctx, hipSetDevice(ctx->device));
     if (N == 0) {  // the prior per component: mean 0, var kdiag_g
         for (int32_t g = 0; g < G; ++g)
             for (int64_t j = 0; j < M; ++j) {
-                double kd = 0.0, pr = 1.0;
-                for (int t = 0; t < T; ++t) {
-                    const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : Xs[(int64_t)tp.col[t] * ldxs + j];
-                    double k = 1.0;
-                    if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
-                    if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
-                    pr *= sel.comp[t] == g ? k : 0.0;
-                    if (tp.last_in_group[t]) {
-                        kd += pr;
-                        pr = 1.0;
-                    }
-                }
                 if (out_mean) out_mean[g * ldm + j] = 0.0;
-                if (out_var) out_var[g * ldv + j] = kd;
+                if (out_var) out_var[g * ldv + j] = host_kdiag(tp, Xs, ldxs, j, &sel, g);
             }
         return 0;
     }
     if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
-    const size_t nxs = (size_t)M * (size_t)(D > 0 ? D : 1);
-    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, nxs))) return rc;
-    if (D > 0)
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)M * 8, Xs, (size_t)ldxs * 8, (size_t)M * 8, (size_t)D,
-                                    hipMemcpyHostToDevice, ctx->s_main));
+    if ((rc = upload_test_inputs(ctx, D, M, 0, M, Xs, ldxs))) return rc;
     tp.noise = noise;
-    ctx->xr_mode = 2;
-    ctx->xr_tiles = (int)((R + NB - 1) / NB);
-    ctx->xr_M = R;
-    ctx->xr_comp = true;
-    ctx->xr_sel = sel;
     EvalResult r;
-    rc = eval_device(ctx, N, D, tp, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    ctx->xr_comp = false;
-    if (rc) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows::components(sel), &r))) return rc;
     rc = finish(r, nullptr, nullptr, nullptr);
     if (rc) return rc;
     // (pmean / pvar hold the G columns packed, leading dimension M)
@@ -1547,7 +1631,7 @@ int posterior_components_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
 }
 
 // Shared body of gaplac_logpdf_multi / _device: one factorisation, the R responses as
-// dense extra rows (xr_mode 3). Column 0 also rides in row N as v (the evaluation's own
+// dense extra rows (ExtraRows::responses). Column 0 also rides in row N as v (the evaluation's own
 // quad is not used: all R results come from the extra rows, one code path per column).
 int logpdf_multi_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const double* X, int64_t ldx,
                       int32_t T, const gaplac_term* terms, double noise, int64_t R, const double* Y, int64_t ldy,
@@ -1578,24 +1662,14 @@ int logpdf_multi_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, con
     tp.noise = noise;
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, Y, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
-    ctx->xr_Y = Y;
-    ctx->xr_ldy = ldy;
     if (!on_device) {
         if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)N * (size_t)R))) return rc;
         HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)N * 8, Y, (size_t)ldy * 8, (size_t)N * 8, (size_t)R,
                                     hipMemcpyHostToDevice, ctx->s_main));
-        ctx->xr_Y = ctx->dY;
-        ctx->xr_ldy = N;
     }
-    ctx->xr_mode = 3;
-    ctx->xr_tiles = (int)((R + NB - 1) / NB);
-    ctx->xr_M = R;
     EvalResult r;
-    rc = eval_device(ctx, N, D, tp, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    ctx->xr_Y = nullptr;
-    if (rc) return rc;
+    const ExtraRows xr = on_device ? ExtraRows::responses(R, Y, ldy) : ExtraRows::responses(R, ctx->dY, N);
+    if ((rc = eval_device(ctx, N, D, tp, xr, &r))) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;  // PosDefException: every output stays NaN
     if (out_logdet) *out_logdet = r.logdet;
     if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
@@ -1618,97 +1692,86 @@ int joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t 
 // The second factorisation runs in B: A and B change places for as long as this lives.
 struct WsSwap {
     gaplac_ctx* c;
-    explicit WsSwap(gaplac_ctx* ctx) : c(ctx) { flip(true); }
-    ~WsSwap() {
-        flip(false);
-        c->xr_mode = 0;
-        c->xr_tiles = 0;
-        c->xr_Y = nullptr;
-        c->xr_sub = nullptr;
-    }
-    void flip(bool on) {
+    explicit WsSwap(gaplac_ctx* ctx) : c(ctx) { flip(); }
+    ~WsSwap() { flip(); }
+    void flip() {
         std::swap(c->A, c->B);
         std::swap(c->A_elems, c->B_elems);
-        c->preloaded = on;
     }
 };
 
-// Stages 1 and 2: the posterior evaluation (xr_mode 2: V^T below the factor, the mean in
-// ctx->pmean), then, with want_cov, post_cov_kernel writes the augmented matrix of Sigma* into
-// ctx->B, laid out for a factorisation of order M with rows_tiles extra tile rows. tp comes in
-// with the training noise and leaves with noise_s (the pack of stages 2 and 3, also in ctx->dtp).
+// Paddings and leading dimensions of the two workspaces, for the entries and for
+// gaplac_plan_check_joint alike: A of order N with the M test points in mt riding tile rows, B of
+// order M with R responses in rt riding tile rows (R = 0: none).
+struct JointDims {
+    int mt, rt;
+    int64_t Np, Mp, lda, ldb;
+};
+JointDims joint_dims(int64_t N, int64_t M, int64_t R) {
+    JointDims d;
+    d.mt = (int)((M + NB - 1) / NB);
+    d.rt = (int)((R + NB - 1) / NB);
+    d.Np = round_up(N + 1, NB);
+    d.Mp = round_up(M + 1, NB);
+    d.lda = d.Np + (int64_t)NB * d.mt;
+    d.ldb = d.Mp + (int64_t)NB * d.rt;
+    return d;
+}
+
+// Stage 2's launches, run by joint_stages and walked dry by gaplac_plan_check_joint (Xs, mean and
+// dtp may be null there): the augmented matrix of Sigma* into B (row M, the v row, carries the
+// mean: its results are not used), and with `mirror` its upper triangle from the lower.
+void joint_cov_launches(hipStream_t s, const JointDims& d, int64_t N, int64_t M, double* A, double* B,
+                        const double* Xs, const double* mean, const TermPack* dtp, bool mirror) {
+    launch_post_cov(s, A, d.lda, d.Np, N, M, B, d.ldb, Xs, M, mean, dtp);
+    if (mirror) launch_mirror_lower(s, B, d.ldb, M);
+}
+
+// The draws O (N x R, ld N) = L Z (Z with the factor's leading dimension), plus `mean` per
+// column when given: gaplac_rand_multi and gaplac_posterior_rand.
+void draws_launches(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* Z, int64_t R, double* O,
+                    const double* mean) {
+    launch_lower_mm(s, A, lda, N, Z, lda, R, O, N);
+    if (mean) launch_add_mean(s, O, N, N, R, mean);
+}
+
+// Stages 1 and 2: the posterior evaluation (M test points: V^T below the factor, the mean in
+// ctx->pmean), then, unless cov is Cov::none, the augmented matrix of Sigma* into ctx->B, laid
+// out for a factorisation of order M with R riding responses (Cov::full: mirrored into a full
+// matrix). tp comes in with the training noise and leaves with noise_s (the pack of stages 2 and
+// 3, also in ctx->dtp).
+enum class Cov { none, lower, full };
 int joint_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, TermPack& tp, const double* y,
-                 int64_t M, const double* Xs, int64_t ldxs, double noise_s, int rows_tiles, bool want_cov) {
+                 int64_t M, const double* Xs, int64_t ldxs, double noise_s, int64_t R, Cov cov) {
     int rc;
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
-    const size_t nxs = (size_t)M * (size_t)(D > 0 ? D : 1);
-    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, nxs))) return rc;
-    if (D > 0)
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)M * 8, Xs, (size_t)ldxs * 8, (size_t)M * 8, (size_t)D,
-                                    hipMemcpyHostToDevice, ctx->s_main));
-    const int mt = (int)((M + NB - 1) / NB);
-    ctx->xr_mode = 2;
-    ctx->xr_tiles = mt;
-    ctx->xr_M = M;
+    if ((rc = upload_test_inputs(ctx, D, M, 0, M, Xs, ldxs))) return rc;
     EvalResult r;
-    rc = eval_device(ctx, N, D, tp, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    if (rc) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows::test_points(M), &r))) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr)))
         return set_err(ctx, rc, "the training covariance K(X) + noise I is not positive definite (leading minor %d)", rc);
-    if (!want_cov) return 0;
-    const int64_t Np = round_up(N + 1, NB), lda = Np + (int64_t)NB * mt;
-    const int64_t Mp = round_up(M + 1, NB), ldb = Mp + (int64_t)NB * rows_tiles;
-    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)ldb * (size_t)Mp))) return rc;
+    if (cov == Cov::none) return 0;
+    const JointDims d = joint_dims(N, M, R);
+    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)d.ldb * (size_t)d.Mp))) return rc;
     tp.noise = noise_s;
     *ctx->htp = tp;  // (stage 1 has retired: eval_device waited for it)
     HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, ctx->s_main));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // diagnostics (GAPLAC_TAIL_TRACE): "N M ms" of the covariance launches alone, appended to <trace path>.pc
-    const bool timed = !ctx->ttrace_path.empty();
-    if (timed) {
-        HIPCK(ctx, hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            (void)hipEventDestroy(ev[0]);
-            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
-        }
-        (void)hipEventRecord(ev[0], ctx->s_main);
-    }
-    LaunchGuard g;
-    g.base = ctx->A;
-    g.elems = (int64_t)ctx->A_elems;
-    g.base2 = ctx->B;
-    g.elems2 = (int64_t)ctx->B_elems;
-    {
-        GuardScope scope(&g);
-        // row M of B (the v row) carries the mean: its results are not used
-        launch_post_cov(ctx->s_main, ctx->A, lda, Np, N, M, ctx->B, ldb, ctx->dXs, M, ctx->pmean, ctx->dtp);
-    }
-    if (timed) {
-        float ms = 0.f;
-        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
-        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".pc").c_str(), "a") : nullptr) {
-            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)M, (double)ms);
-            std::fclose(f);
-        }
-    }
-    if (g.violations)
-        return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    HIPCK(ctx, hipGetLastError());
-    return 0;
+    // <trace path>.pc: "N M ms" of the covariance launches alone
+    return trace_timed(ctx, ".pc", N, M, [&] {
+        return guarded(ctx, true, [&] {
+            joint_cov_launches(ctx->s_main, d, N, M, ctx->A, ctx->B, ctx->dXs, ctx->pmean, ctx->dtp, cov == Cov::full);
+        });
+    });
 }
 
 // Stage 3: the factorisation of order M of the matrix in ctx->B (A and B already swapped by the
-// caller's WsSwap; xr_mode / xr_tiles set for riding rows). info > 0: the leading minor of Sigma*
-// (or of the matrix `what` names: the sparse entries factor their S the same way, §10.8).
-int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, EvalResult* r,
+// caller's WsSwap), which xr describes as prebuilt, with or without riding rows. info > 0: the
+// leading minor of Sigma* (or of the matrix `what` names: the sparse entries factor their S the
+// same way, §10.8).
+int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, const ExtraRows& xr, EvalResult* r,
                  const char* what = "the test-point covariance Sigma*") {
-    int rc = eval_device(ctx, M, D, tp, r);
+    int rc = eval_device(ctx, M, D, tp, xr, r);
     if (rc) return rc;
     if ((rc = finish(*r, nullptr, nullptr, nullptr)))
         return set_err(ctx, rc, "%s is not positive definite (leading minor %d)", what, rc);
@@ -1736,22 +1799,11 @@ int posterior_mean_cov_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double*
         return 0;
     }
     tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, out_cov != nullptr))) return rc;
-    if (out_cov) {
-        const int64_t ldb = round_up(M + 1, NB);
-        LaunchGuard g;
-        g.base2 = ctx->B;
-        g.elems2 = (int64_t)ctx->B_elems;
-        {
-            GuardScope scope(&g);
-            launch_mirror_lower(ctx->s_main, ctx->B, ldb, M);
-        }
-        if (g.violations)
-            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-        HIPCK(ctx, hipGetLastError());
-        HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)ldb * 8, (size_t)M * 8, (size_t)M,
-                                    hipMemcpyDeviceToHost, ctx->s_main));
-    }
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, out_cov ? Cov::full : Cov::none)))
+        return rc;
+    if (out_cov)
+        HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)joint_dims(N, M, 0).ldb * 8,
+                                    (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost, ctx->s_main));
     if (out_mean)
         HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
@@ -1775,26 +1827,18 @@ int posterior_rand_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     if (N == 0)  // the prior at the test points
         return gaplac_rand_multi(ctx, M, D, Xs, ldxs, T, terms, noise_s, R, Z, ldz, out, ldo);
     tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, true))) return rc;
-    const int64_t Mp = round_up(M + 1, NB);
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, Cov::lower))) return rc;
+    const int64_t Mp = joint_dims(N, M, 0).Mp;
     if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Mp * (size_t)R))) return rc;
     if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)M * (size_t)R))) return rc;
     HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Mp * 8, Z, (size_t)ldz * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyHostToDevice, ctx->s_main));
     WsSwap swap(ctx);  // from here on ctx->A is the order-M workspace
     EvalResult r2;
-    if ((rc = joint_factor(ctx, M, D, tp, &r2))) return rc;
-    {
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_lower_mm(ctx->s_main, ctx->A, Mp, M, ctx->dZ, Mp, R, ctx->dO, M);
-        launch_add_mean(ctx->s_main, ctx->dO, M, M, R, ctx->pmean);
-        if (g.violations)
-            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    }
-    HIPCK(ctx, hipGetLastError());
+    if ((rc = joint_factor(ctx, M, D, tp, ExtraRows{}.on_prebuilt(), &r2))) return rc;
+    if ((rc = guarded(ctx, false,
+                      [&] { draws_launches(ctx->s_main, ctx->A, Mp, M, ctx->dZ, R, ctx->dO, ctx->pmean); })))
+        return rc;
     HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)M * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
@@ -1825,22 +1869,16 @@ int posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
                                    out_quad);
     if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
         return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
-    const int rt = (int)((R + NB - 1) / NB);
     tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, rt, true))) return rc;
+    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, R, Cov::lower))) return rc;
     if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)M * (size_t)R))) return rc;
     HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)M * 8, Ys, (size_t)ldys * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyHostToDevice, ctx->s_main));
     WsSwap swap(ctx);
     // the rows hold (Ys - m 1^T)^T and ride along as the responses of gaplac_logpdf_multi do
-    ctx->xr_mode = 3;
-    ctx->xr_tiles = rt;
-    ctx->xr_M = R;
-    ctx->xr_Y = ctx->dY;
-    ctx->xr_ldy = M;
-    ctx->xr_sub = ctx->pmean;
     EvalResult r2;
-    if ((rc = joint_factor(ctx, M, D, tp, &r2))) return rc;
+    if ((rc = joint_factor(ctx, M, D, tp, ExtraRows::responses(R, ctx->dY, M, ctx->pmean).on_prebuilt(), &r2)))
+        return rc;
     if (out_logdet) *out_logdet = r2.logdet;
     if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
     HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
@@ -1864,23 +1902,6 @@ void sparse_split(int64_t N, int64_t Mz, int64_t* chunks, int64_t* chunk_rows) {
     *chunks = (N + rows - 1) / rows;
 }
 
-// k(x_j, x_j) of row j of a host matrix (the prior variance; a NOISE term counts).
-double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j) {
-    double kd = 0.0, pr = 1.0;
-    for (int t = 0; t < tp.T; ++t) {
-        const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + j];
-        double k = 1.0;
-        if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
-        if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
-        pr *= k;
-        if (tp.last_in_group[t]) {
-            kd += pr;
-            pr = 1.0;
-        }
-    }
-    return kd;
-}
-
 // Argument checks the two entries share, after their own (output pointers).
 int sparse_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise, const double* y,
                  int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs) {
@@ -1898,85 +1919,78 @@ int sparse_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t
     return 0;
 }
 
-// Stages 1 and 2. Stage 1 is the posterior evaluation (xr_mode 2) of the training set (Z, jitter)
-// with v = 0 and the N rows of X, then the Ms rows of Xs, as its test points: V^T (and a_j^T)
-// below the factor, k(x, x) - |row|^2 in ctx->pvar; *trace = the sum of the first N of those, in
-// order. Stage 2 writes the augmented matrix of S into ctx->B, laid out for a factorisation of
-// order Mz with rows_tiles extra tile rows. tp carries noise = sigma^2 (the pack of stage 3).
+// Paddings, leading dimensions and the stage-2 split, for the entries and for
+// gaplac_plan_check_sparse alike: A of order Mz with the N + Ms rows of X and Xs in mt riding tile
+// rows, B of order Mz (ntb tile columns) with the Ms rows a_j in rt riding tile rows (Ms = 0: none).
+struct SparseDims {
+    int mt, rt;
+    int64_t Np, lda, ldb, ntb, chunks, chunk_rows;
+};
+SparseDims sparse_dims(int64_t N, int64_t Mz, int64_t Ms) {
+    SparseDims d;
+    d.mt = (int)((N + Ms + NB - 1) / NB);
+    d.rt = (int)((Ms + NB - 1) / NB);
+    d.Np = round_up(Mz + 1, NB);
+    d.lda = d.Np + (int64_t)NB * d.mt;
+    d.ldb = d.Np + (int64_t)NB * d.rt;
+    d.ntb = d.Np / NB;
+    sparse_split(N, Mz, &d.chunks, &d.chunk_rows);
+    return d;
+}
+
+// The launches after an evaluation, run by the entries and walked dry by gaplac_plan_check_sparse
+// (the buffers besides A and B may be null there). Stage 2: the augmented matrix of S into B.
+void sparse_s_launches(hipStream_t s, const SparseDims& d, int64_t N, int64_t Mz, double* A, const double* y,
+                       double* part, double* B, double noise) {
+    launch_rows_syrk(s, A, d.lda, d.Np, Mz, N, (int64_t)NB * d.mt, y, d.chunks, d.chunk_rows, part, B, d.ldb, noise);
+}
+// Y (Mz x Ms, ld Mz) = the a_j rows of stage 1 (riding rows N .. N + Ms - 1), transposed
+void sparse_rows_launches(hipStream_t s, const SparseDims& d, int64_t N, int64_t Mz, int64_t Ms, const double* A,
+                          double* Y) {
+    launch_rows_to_matrix(s, A, d.lda, d.Np, N, Mz, Ms, Y, Mz);
+}
+// mode 2's reduction over the rows of stage 3 (A: the workspace of S): the dot with the v row (u)
+// and the row norm
+void sparse_post_launches(hipStream_t s, const SparseDims& d, int64_t Mz, int64_t Ms, double noise, const double* A,
+                          double* partial, double* mean, double* var) {
+    launch_sparse_post(s, A, d.ldb, d.Np, Mz, Ms, noise, partial, mean, var);
+}
+
+// Stages 1 and 2. Stage 1 is the posterior evaluation of the training set (Z, jitter) with v = 0
+// and the N rows of X, then the Ms rows of Xs, as its test points: V^T (and a_j^T) below the
+// factor, k(x, x) - |row|^2 in ctx->pvar; *trace = the sum of the first N of those, in order.
+// Stage 2 writes the augmented matrix of S into ctx->B, laid out for a factorisation of order Mz
+// with the Ms rows riding. tp carries noise = sigma^2 (the pack of stage 3).
 int sparse_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, const TermPack& tp,
                   const double* y, int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms,
-                  const double* Xs, int64_t ldxs, int rows_tiles, double* trace) {
+                  const double* Xs, int64_t ldxs, double* trace) {
     int rc;
     HIPCK(ctx, hipSetDevice(ctx->device));
     const std::vector<double> zeros((size_t)Mz, 0.0);
     if ((rc = upload(ctx, Mz, D, Z, ldz, zeros.data()))) return rc;
     const int64_t R = N + Ms;
-    if ((rc = ensure(ctx, &ctx->dXs, &ctx->dXs_elems, (size_t)R * (size_t)(D > 0 ? D : 1)))) return rc;
-    if (D > 0) {
-        HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs, (size_t)R * 8, X, (size_t)ldx * 8, (size_t)N * 8, (size_t)D,
-                                    hipMemcpyHostToDevice, ctx->s_main));
-        if (Ms > 0)
-            HIPCK(ctx, hipMemcpy2DAsync(ctx->dXs + N, (size_t)R * 8, Xs, (size_t)ldxs * 8, (size_t)Ms * 8, (size_t)D,
-                                        hipMemcpyHostToDevice, ctx->s_main));
-    }
+    if ((rc = upload_test_inputs(ctx, D, R, 0, N, X, ldx))) return rc;
+    if ((rc = upload_test_inputs(ctx, D, R, N, Ms, Xs, ldxs))) return rc;
     if ((rc = ensure(ctx, &ctx->sp_y, &ctx->sp_y_elems, (size_t)N))) return rc;
     HIPCK(ctx, hipMemcpyAsync(ctx->sp_y, y, (size_t)N * 8, hipMemcpyHostToDevice, ctx->s_main));
-    const int mt = (int)((R + NB - 1) / NB);
     TermPack tp1 = tp;
     tp1.noise = jitter;
-    ctx->xr_mode = 2;
-    ctx->xr_tiles = mt;
-    ctx->xr_M = R;
     EvalResult r;
-    rc = eval_device(ctx, Mz, D, tp1, &r);
-    ctx->xr_mode = 0;
-    ctx->xr_tiles = 0;
-    if (rc) return rc;
+    if ((rc = eval_device(ctx, Mz, D, tp1, ExtraRows::test_points(R), &r))) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr)))
         return set_err(ctx, rc, "the inducing covariance K(Z) + jitter I is not positive definite (leading minor %d)", rc);
-    const int64_t Np = round_up(Mz + 1, NB), lda = Np + (int64_t)NB * mt;
-    const int64_t ldb = Np + (int64_t)NB * rows_tiles, ntb = Np / NB;
-    int64_t chunks, chunk_rows;
-    sparse_split(N, Mz, &chunks, &chunk_rows);
-    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)ldb * (size_t)Np))) return rc;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
+    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)d.ldb * (size_t)d.Np))) return rc;
     if ((rc = ensure(ctx, &ctx->sp_part, &ctx->sp_part_elems,
-                     (size_t)chunks * (size_t)(ntb * (ntb + 1) / 2) * (size_t)(NB * NB))))
+                     (size_t)d.chunks * (size_t)(d.ntb * (d.ntb + 1) / 2) * (size_t)(NB * NB))))
         return rc;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // diagnostics (GAPLAC_TAIL_TRACE): "N Mz ms" of the stage-2 launches alone, appended to <trace path>.ss
-    const bool timed = !ctx->ttrace_path.empty();
-    if (timed) {
-        HIPCK(ctx, hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            (void)hipEventDestroy(ev[0]);
-            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
-        }
-        (void)hipEventRecord(ev[0], ctx->s_main);
-    }
-    LaunchGuard g;
-    g.base = ctx->A;
-    g.elems = (int64_t)ctx->A_elems;
-    g.base2 = ctx->B;
-    g.elems2 = (int64_t)ctx->B_elems;
-    {
-        GuardScope scope(&g);
-        launch_rows_syrk(ctx->s_main, ctx->A, lda, Np, Mz, N, (int64_t)NB * mt, ctx->sp_y, chunks, chunk_rows,
-                         ctx->sp_part, ctx->B, ldb, tp.noise);
-    }
-    if (timed) {
-        float ms = 0.f;
-        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
-        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".ss").c_str(), "a") : nullptr) {
-            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)Mz, (double)ms);
-            std::fclose(f);
-        }
-    }
-    if (g.violations)
-        return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    HIPCK(ctx, hipGetLastError());
+    // <trace path>.ss: "N Mz ms" of the stage-2 launches alone
+    rc = trace_timed(ctx, ".ss", N, Mz, [&] {
+        return guarded(ctx, true, [&] {
+            sparse_s_launches(ctx->s_main, d, N, Mz, ctx->A, ctx->sp_y, ctx->sp_part, ctx->B, tp.noise);
+        });
+    });
+    if (rc) return rc;
     if (trace) {  // (stage 1 has retired: eval_device waited for it)
         std::vector<double> pv((size_t)N);
         HIPCK(ctx, hipMemcpy(pv.data(), ctx->pvar, (size_t)N * 8, hipMemcpyDeviceToHost));
@@ -2011,10 +2025,10 @@ int sparse_elbo_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int
         logdet = (double)N * std::log(noise);
         quad = yty / noise;
     } else if (N > 0) {
-        if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, 0, nullptr, 0, 0, &trace))) return rc;
+        if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, 0, nullptr, 0, &trace))) return rc;
         WsSwap swap(ctx);  // from here on ctx->A is the workspace of S
         EvalResult r2;
-        if ((rc = joint_factor(ctx, Mz, D, tp, &r2, SPARSE_S))) return rc;
+        if ((rc = joint_factor(ctx, Mz, D, tp, ExtraRows{}.on_prebuilt(), &r2, SPARSE_S))) return rc;
         logdet = (double)(N - Mz) * std::log(noise) + r2.logdet;
         quad = (yty - r2.quad) / noise;
     }
@@ -2049,42 +2063,21 @@ int sparse_posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
         return 0;
     }
     tp.noise = noise;
-    const int rt = (int)((Ms + NB - 1) / NB);
-    if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, rt, nullptr))) return rc;
-    const int64_t Np = round_up(Mz + 1, NB);
-    const int64_t lda = Np + (int64_t)NB * ((N + Ms + NB - 1) / NB), ldb = Np + (int64_t)NB * rt;
-    // the a_j rows of stage 1, transposed, are the matrix whose columns ride stage 3 (xr_mode 3's row source)
+    if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, nullptr))) return rc;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
+    // the a_j rows of stage 1, transposed, are the matrix whose columns ride stage 3 (mode 3's row source)
     if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)Mz * (size_t)Ms))) return rc;
     if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, 2 * (size_t)Ms * (size_t)((Mz + 511) / 512)))) return rc;
-    {
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_rows_to_matrix(ctx->s_main, ctx->A, lda, Np, N, Mz, Ms, ctx->dY, Mz);
-        if (g.violations)
-            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    }
-    HIPCK(ctx, hipGetLastError());
+    if ((rc = guarded(ctx, false, [&] { sparse_rows_launches(ctx->s_main, d, N, Mz, Ms, ctx->A, ctx->dY); })))
+        return rc;
     WsSwap swap(ctx);
-    ctx->xr_mode = 3;
-    ctx->xr_tiles = rt;
-    ctx->xr_M = Ms;
-    ctx->xr_Y = ctx->dY;
-    ctx->xr_ldy = Mz;
     EvalResult r2;
-    if ((rc = joint_factor(ctx, Mz, D, tp, &r2, SPARSE_S))) return rc;
-    {
-        // mode 2's reduction over the rows of stage 3: the dot with the v row (u) and the row norm
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_sparse_post(ctx->s_main, ctx->A, ldb, Np, Mz, Ms, noise, ctx->gpart, ctx->pmean, ctx->pvar + N);
-        if (g.violations)
-            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    }
-    HIPCK(ctx, hipGetLastError());
+    if ((rc = joint_factor(ctx, Mz, D, tp, ExtraRows::responses(Ms, ctx->dY, Mz).on_prebuilt(), &r2, SPARSE_S)))
+        return rc;
+    if ((rc = guarded(ctx, false, [&] {
+             sparse_post_launches(ctx->s_main, d, Mz, Ms, noise, ctx->A, ctx->gpart, ctx->pmean, ctx->pvar + N);
+         })))
+        return rc;
     if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
     if (out_var)
         HIPCK(ctx, hipMemcpyAsync(out_var, ctx->pvar + N, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
@@ -2221,12 +2214,14 @@ static int batch_tail_finish(gaplac_ctx* ctx, int p, double* out_logpdf, int64_t
     return 0;
 }
 
-// A host-only walk of one evaluation's schedule (both plan checks): c, a context on the
-// stack with its switches and extra-row mode set, gets the workspace size and tile layout
-// ensure_workspace would give it for order N behind a fake pointer (never dereferenced:
-// the walk only does pointer arithmetic against the guard's base), and the schedule is
-// enqueued dry under g, whose workspace is short_by elements short (the negative control).
-static int dry_walk(gaplac_ctx& c, int64_t N, LaunchGuard& g, int64_t short_by = 0) {
+// A host-only walk of one evaluation's schedule (every plan check): c, a context on the
+// stack with its switches set, carries the description xr as an evaluation would (EvalScope)
+// and gets the workspace size and tile layout ensure_workspace would give it for order N
+// behind a fake pointer (never dereferenced: the walk only does pointer arithmetic against
+// the guard's base); the schedule is enqueued dry under g, whose workspace is short_by
+// elements short (the negative control).
+static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& g, int64_t short_by = 0) {
+    EvalScope scope(&c, xr);
     const int64_t Np = round_up(N + 1, NB);
     const int nt = (int)(Np / NB);
     double* const fake = reinterpret_cast<double*>((uintptr_t)1 << 44);
@@ -2235,12 +2230,12 @@ static int dry_walk(gaplac_ctx& c, int64_t N, LaunchGuard& g, int64_t short_by =
     c.dry = true;
     c.tail_s = 80;  // as gaplac_ctx_create sets it with the persistent tail
     c.A = c.Dinv = fake;
-    c.A_elems = (size_t)(Np + (int64_t)NB * c.xr_tiles) * (size_t)Np;
+    c.A_elems = (size_t)(Np + (int64_t)NB * c.xr.tiles) * (size_t)Np;
     c.tiles = reinterpret_cast<uint32_t*>(fake);
     c.htp = &tp;
     set_tile_layout(&c, nt);
     c.tiles_nt = nt;
-    if (c.xr_mode == 1) {
+    if (c.xr.mode == 1) {
         std::vector<uint32_t> gl;
         build_grad_list((int)((N + NB - 1) / NB), gl);
         c.glist_blocks = (int)gl.size();
@@ -2250,7 +2245,7 @@ static int dry_walk(gaplac_ctx& c, int64_t N, LaunchGuard& g, int64_t short_by =
     g.dry = true;
     int rc;
     {
-        GuardScope scope(&g);
+        GuardScope gscope(&g);
         rc = enqueue_eval(&c, N, 1, Np, nt);
     }
     c.htp = nullptr;  // nothing of the walk's stays behind in c
@@ -2530,15 +2525,10 @@ int gaplac_gram(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t 
     tp.noise = noise;
     *ctx->htp = tp;
     HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, ctx->s_main));
-    {
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_gram(ctx->s_main, ctx->A, Np, N, nt, ctx->dX, N, ctx->dv, ctx->dtp, 0, 0, nullptr);
-        if (g.violations) return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    }
-    HIPCK(ctx, hipGetLastError());
+    if ((rc = guarded(ctx, false, [&] {
+             launch_gram(ctx->s_main, ctx->A, Np, N, nt, ctx->dX, N, ctx->dv, ctx->dtp, 0, 0, nullptr);
+         })))
+        return rc;
     HIPCK(ctx, hipMemcpy2DAsync(out_C, (size_t)ldc * 8, ctx->A, (size_t)Np * 8, (size_t)N * 8,
                                 (size_t)N, hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
@@ -2608,7 +2598,7 @@ int gaplac_factor(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_
     if ((rc = upload(ctx, N, D, X, ldx, v))) return rc;
     tp.noise = noise;
     EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}, &r))) return rc;
     const int64_t Np = round_up(N + 1, NB);
     HIPCK(ctx, hipMemcpy2D(out_L, (size_t)ldl * 8, ctx->A, (size_t)Np * 8, (size_t)N * 8, (size_t)N,
                            hipMemcpyDeviceToHost));
@@ -2660,21 +2650,15 @@ int gaplac_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t 
     if ((rc = upload(ctx, N, D, X, ldx, z))) return rc;  // z also rides in the v row (unused)
     tp.noise = noise;
     EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}, &r))) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;
     const size_t nk = (size_t)((N + 511) / 512);
     if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, nk * (size_t)N))) return rc;
     if ((rc = ensure(ctx, &ctx->gdv, &ctx->gdv_elems, (size_t)N))) return rc;
     const int64_t Np = round_up(N + 1, NB);
-    {
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_lower_mv(ctx->s_main, ctx->A, Np, N, ctx->dv, ctx->gpart, ctx->gdv);
-        if (g.violations) return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-    }
-    HIPCK(ctx, hipGetLastError());
+    if ((rc = guarded(ctx, false,
+                      [&] { launch_lower_mv(ctx->s_main, ctx->A, Np, N, ctx->dv, ctx->gpart, ctx->gdv); })))
+        return rc;
     HIPCK(ctx, hipMemcpyAsync(out, ctx->gdv, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
     return 0;
@@ -2714,42 +2698,14 @@ int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, in
                                 hipMemcpyHostToDevice, ctx->s_main));
     tp.noise = noise;
     EvalResult r;
-    if ((rc = eval_device(ctx, N, D, tp, &r))) return rc;
+    if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}, &r))) return rc;
     if ((rc = finish(r, nullptr, nullptr, nullptr))) return rc;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    // diagnostics (GAPLAC_TAIL_TRACE): "N R ms" of the L Z launch alone, appended to <trace path>.lz
-    const bool timed = !ctx->ttrace_path.empty();
-    if (timed) {
-        HIPCK(ctx, hipEventCreate(&ev[0]));
-        if (hipEventCreate(&ev[1]) != hipSuccess) {
-            (void)hipEventDestroy(ev[0]);
-            return set_err(ctx, GAPLAC_E_HIP, "hipEventCreate failed");
-        }
-        (void)hipEventRecord(ev[0], ctx->s_main);
-    }
-    {
-        LaunchGuard g;
-        g.base = ctx->A;
-        g.elems = (int64_t)ctx->A_elems;
-        GuardScope scope(&g);
-        launch_lower_mm(ctx->s_main, ctx->A, Np, N, ctx->dZ, Np, R, ctx->dO, N);
-        if (g.violations) {
-            if (timed) (void)hipEventDestroy(ev[0]), (void)hipEventDestroy(ev[1]);
-            return set_err(ctx, GAPLAC_E_ARG, "launch footprint outside the workspace: %s", g.first.c_str());
-        }
-    }
-    if (timed) {
-        float ms = 0.f;
-        const bool ok = hipEventRecord(ev[1], ctx->s_main) == hipSuccess && hipEventSynchronize(ev[1]) == hipSuccess &&
-                        hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
-        if (FILE* f = ok ? std::fopen((ctx->ttrace_path + ".lz").c_str(), "a") : nullptr) {
-            std::fprintf(f, "%lld %lld %.6f\n", (long long)N, (long long)R, (double)ms);
-            std::fclose(f);
-        }
-    }
-    HIPCK(ctx, hipGetLastError());
+    // <trace path>.lz: "N R ms" of the L Z launch alone
+    rc = trace_timed(ctx, ".lz", N, R, [&] {
+        return guarded(ctx, false,
+                       [&] { draws_launches(ctx->s_main, ctx->A, Np, N, ctx->dZ, R, ctx->dO, nullptr); });
+    });
+    if (rc) return rc;
     HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)N * 8, (size_t)N * 8, (size_t)R,
                                 hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
@@ -2801,57 +2757,46 @@ int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out
 }
 
 // Host-only walk of the sparse entries' three stages (no device needed): the posterior
-// evaluation of order Mz with N + Ms riding rows, the stage-2 launches (and, with Ms > 0, the
-// transposing copy) against both workspaces, and the preloaded factorisation of order Mz, plain
-// (Ms = 0, gaplac_sparse_elbo) or with Ms riding rows and their reduction
-// (gaplac_sparse_posterior_mean_var). short_ws 1 / 2: the stage-1 / stage-3 workspace one element
-// short (negative controls).
+// evaluation of order Mz with N + Ms riding rows, the stage-2 launches and the transposing copy
+// against both workspaces, and the prebuilt factorisation of order Mz, plain (Ms = 0,
+// gaplac_sparse_elbo) or with Ms riding rows (gaplac_sparse_posterior_mean_var), and the rows'
+// reduction. The launches between the evaluations are the entries' own functions, run dry; the
+// walk takes the copy and the reduction at Ms = 0 too, where the entries have neither. short_ws
+// 1 / 2: the stage-1 / stage-3 workspace one element short (negative controls).
 int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws, int64_t* out_launches,
                              int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || Mz < 1 || Ms < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
     if ((N + Ms + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
-    const int64_t Np = round_up(Mz + 1, NB);
-    const int mt = (int)((N + Ms + NB - 1) / NB), rt = (int)((Ms + NB - 1) / NB);
-    const int64_t lda = Np + (int64_t)NB * mt, ldb = Np + (int64_t)NB * rt;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
     double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
     double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    const int64_t a_elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0), b_elems = d.ldb * d.Np - (short_ws == 2 ? 1 : 0);
     LaunchGuard g1, g2, g3, g4;
-    gaplac_ctx c1;
-    c1.spw = spw;
-    c1.xr_mode = 2;
-    c1.xr_tiles = mt;
-    c1.xr_M = N + Ms;
-    int rc = dry_walk(c1, Mz, g1, short_ws == 1 ? 1 : 0);
+    gaplac_ctx c1, c3;
+    c1.spw = c3.spw = spw;
+    int rc = dry_walk(c1, Mz, ExtraRows::test_points(N + Ms), g1, short_ws == 1 ? 1 : 0);
     if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
     if (rc == 0) {
         g2.base = fa;
-        g2.elems = lda * Np - (short_ws == 1 ? 1 : 0);
+        g2.elems = a_elems;
         g2.base2 = fb;
-        g2.elems2 = ldb * Np - (short_ws == 2 ? 1 : 0);
+        g2.elems2 = b_elems;
         g2.dry = true;
         GuardScope scope(&g2);
-        int64_t chunks, chunk_rows;
-        sparse_split(N, Mz, &chunks, &chunk_rows);
-        launch_rows_syrk(nullptr, fa, lda, Np, Mz, N, (int64_t)NB * mt, nullptr, chunks, chunk_rows, nullptr, fb, ldb,
-                         1.0);
-        launch_rows_to_matrix(nullptr, fa, lda, Np, N, Mz, Ms, nullptr, Mz);
+        sparse_s_launches(nullptr, d, N, Mz, fa, nullptr, nullptr, fb, 1.0);
+        sparse_rows_launches(nullptr, d, N, Mz, Ms, fa, nullptr);
     }
     if (rc == 0) {
-        gaplac_ctx c3;
-        c3.spw = spw;
-        c3.preloaded = true;
-        c3.xr_mode = Ms > 0 ? 3 : 0;
-        c3.xr_tiles = rt;
-        c3.xr_M = Ms;
-        rc = dry_walk(c3, Mz, g3, short_ws == 2 ? 1 : 0);
+        const ExtraRows rows = Ms > 0 ? ExtraRows::responses(Ms, nullptr, 0) : ExtraRows{};
+        rc = dry_walk(c3, Mz, rows.on_prebuilt(), g3, short_ws == 2 ? 1 : 0);
         if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
     }
     if (rc == 0) {
         g4.base = fb;
-        g4.elems = ldb * Np - (short_ws == 2 ? 1 : 0);
+        g4.elems = b_elems;
         g4.dry = true;
         GuardScope scope(&g4);
-        launch_sparse_post(nullptr, fb, ldb, Np, Mz, Ms, 1.0, nullptr, nullptr, nullptr);
+        sparse_post_launches(nullptr, d, Mz, Ms, 1.0, fb, nullptr, nullptr, nullptr);
     }
     if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches + g4.launches;
     if (out_violations) *out_violations = g1.violations + g2.violations + g3.violations + g4.violations;
@@ -2862,43 +2807,36 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior
 // evaluation of order N with M test points, the covariance launches (zeroing, post_cov_kernel,
-// the mirroring pass) against both workspaces, and the preloaded factorisation of order M, with
+// the mirroring pass) against both workspaces, and the prebuilt factorisation of order M, with
 // R > 0 carrying R riding rows (gaplac_posterior_logpdf), else plain (gaplac_posterior_rand).
+// The covariance launches are the entries' own function, run dry. Two gaps against the entries:
+// the walk takes the mirroring pass whenever R = 0, the entries when a covariance is asked for
+// (gaplac_posterior_mean_cov with out_cov; gaplac_posterior_rand has none); and
+// gaplac_posterior_rand's draws_launches after stage 3 are in no walk.
 // short_ws 1 / 2: the order-N / order-M workspace one element short (negative controls).
 int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_t short_ws, int64_t* out_launches,
                             int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || M < 1 || R < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
-    const int64_t Np = round_up(N + 1, NB), Mp = round_up(M + 1, NB);
-    const int mt = (int)((M + NB - 1) / NB), rt = (int)((R + NB - 1) / NB);
-    const int64_t lda = Np + (int64_t)NB * mt, ldb = Mp + (int64_t)NB * rt;
+    const JointDims d = joint_dims(N, M, R);
     LaunchGuard g1, g2, g3;
-    gaplac_ctx c1;
-    c1.spw = spw;
-    c1.xr_mode = 2;
-    c1.xr_tiles = mt;
-    c1.xr_M = M;
-    int rc = dry_walk(c1, N, g1, short_ws == 1 ? 1 : 0);
+    gaplac_ctx c1, c3;
+    c1.spw = c3.spw = spw;
+    int rc = dry_walk(c1, N, ExtraRows::test_points(M), g1, short_ws == 1 ? 1 : 0);
     if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
     if (rc == 0) {
         double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
         double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
         g2.base = fa;
-        g2.elems = lda * Np - (short_ws == 1 ? 1 : 0);
+        g2.elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0);
         g2.base2 = fb;
-        g2.elems2 = ldb * Mp - (short_ws == 2 ? 1 : 0);
+        g2.elems2 = d.ldb * d.Mp - (short_ws == 2 ? 1 : 0);
         g2.dry = true;
         GuardScope scope(&g2);
-        launch_post_cov(nullptr, fa, lda, Np, N, M, fb, ldb, nullptr, M, nullptr, nullptr);
-        if (R == 0) launch_mirror_lower(nullptr, fb, ldb, M);
+        joint_cov_launches(nullptr, d, N, M, fa, fb, nullptr, nullptr, nullptr, R == 0);
     }
     if (rc == 0) {
-        gaplac_ctx c3;
-        c3.spw = spw;
-        c3.preloaded = true;
-        c3.xr_mode = R > 0 ? 3 : 0;
-        c3.xr_tiles = rt;
-        c3.xr_M = R;
-        rc = dry_walk(c3, M, g3, short_ws == 2 ? 1 : 0);
+        const ExtraRows rows = R > 0 ? ExtraRows::responses(R, nullptr, 0) : ExtraRows{};
+        rc = dry_walk(c3, M, rows.on_prebuilt(), g3, short_ws == 2 ? 1 : 0);
         if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
     }
     if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches;
@@ -2985,11 +2923,12 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
     }
     gaplac_ctx c;
     c.spw = spw;
-    c.xr_mode = mode;
-    c.xr_tiles = mode == 1 ? (int)(round_up(N + 1, NB) / NB) : mode >= 2 ? (int)((M + NB - 1) / NB) : 0;
-    c.xr_M = mode >= 2 ? M : 0;
+    const ExtraRows xr = mode == 1   ? ExtraRows::identity(N)
+                         : mode == 2 ? ExtraRows::test_points(M)
+                         : mode == 3 ? ExtraRows::responses(M, nullptr, 0)
+                                     : ExtraRows{};
     LaunchGuard g;
-    const int rc = dry_walk(c, N, g, short_ws ? 1 : 0);
+    const int rc = dry_walk(c, N, xr, g, short_ws ? 1 : 0);
     if (out_launches) *out_launches = g.launches;
     if (out_violations) *out_violations = g.violations;
     if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
@@ -3016,7 +2955,7 @@ int gaplac_plan_check_schedule(int64_t N, int32_t spw, int32_t depth, int32_t pa
     LaunchGuard g;
     std::vector<int> acct;
     g.acct = &acct;
-    const int rc = dry_walk(c, N, g);
+    const int rc = dry_walk(c, N, ExtraRows{}, g);
     std::string why;
     char b[200];
     if (rc) why = "the dry walk failed";
