@@ -216,6 +216,16 @@ def elbo(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None, full: bo
     return (ctx or backend.default_context()).sparse_elbo(*args, full=full)
 
 
+def elbo_and_gradient(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):
+    """(elbo, dy, dparam, dnoise, djitter): the bound and its gradient with respect to y, the
+    lowered terms' parameters, the observation variance and the jitter of f(z, jitter), the
+    inducing inputs fixed (gaplac_sparse_elbo_grad). AbstractGPs has no such method: a Julia host
+    differentiates elbo by AD."""
+    _gate()
+    args = _vfe_args(vfe, fx, y)
+    return (ctx or backend.default_context()).sparse_elbo_grad(*args)
+
+
 def dtc(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):
     """AbstractGPs.dtc(VFE(f(z)), f(x, noise), y): log N(y | 0, Q + noise I), the bound without
     its trace term (gaplac_sparse_elbo's out_dtc)."""

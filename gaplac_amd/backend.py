@@ -405,6 +405,21 @@ class Context:
         names = ("elbo", "dtc", "trace", "logdet", "quad")
         return {k: o.value for k, o in zip(names, out)} if full else out[0].value
 
+    def sparse_elbo_grad(self, X, terms, noise: float, y, Z, jitter: float = 0.0):
+        """(elbo, dy, dparam, dnoise, djitter): the bound and its gradient with respect to y, the
+        term parameters, the observation variance and jitter (gaplac_sparse_elbo_grad)."""
+        head, keep, _ = self._sparse_head(X, terms, noise, y, Z, jitter)
+        N, T = head[0], head[4]
+        elbo, dnoise, djitter = c_double(), c_double(), c_double()
+        dy = np.empty(N, dtype=np.float64)
+        dparam = np.empty(T, dtype=np.float64)
+        yb = dy if N else np.empty(1)  # (an empty result still passes valid pointers)
+        pb = dparam if T else np.empty(1)
+        rc = self.lib.gaplac_sparse_elbo_grad(self.h, *head, byref(elbo), yb.ctypes.data_as(c_void_p),
+                                              pb.ctypes.data_as(c_void_p), byref(dnoise), byref(djitter))
+        self._check(rc)
+        return elbo.value, dy, dparam, dnoise.value, djitter.value
+
     def sparse_posterior_mean_var(self, X, terms, noise: float, y, Z, jitter: float, Xs):
         """(mean, var) of the approximate posterior given y at the rows of Xs
         (gaplac_sparse_posterior_mean_var)."""

@@ -239,6 +239,15 @@ struct gaplac_ctx {
     size_t sp_y_elems = 0;
     double* sp_part = nullptr;
     size_t sp_part_elems = 0;
+    // Its gradient: the order-Mz scratch (three column storages of leading
+    // dimension 2 Np), the first factorisation's Dinv kept across the second, and the vectors
+    bool sg_keep = false;  // gaplac_sparse_elbo_grad is running: the stages keep S and Dinv
+    double* sg = nullptr;
+    size_t sg_elems = 0;
+    double* sg_dinv = nullptr;
+    size_t sg_dinv_elems = 0;
+    double* sg_v = nullptr;
+    size_t sg_v_elems = 0;
     // gradient: alpha, partial sums, the XCD-balanced C^{-1} tile list
     double* galpha = nullptr;
     size_t galpha_elems = 0;
@@ -322,7 +331,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        buf(&c->hgp, sizeof(GradTermPack), true), buf(&c->glist), large(&c->dY, &c->dY_elems),
                        buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems),
                        large(&c->B, &c->B_elems), large(&c->sp_y, &c->sp_y_elems),
-                       large(&c->sp_part, &c->sp_part_elems)};
+                       large(&c->sp_part, &c->sp_part_elems), large(&c->sg, &c->sg_elems),
+                       large(&c->sg_dinv, &c->sg_dinv_elems), large(&c->sg_v, &c->sg_v_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -1400,13 +1410,22 @@ int upload_test_inputs(gaplac_ctx* ctx, int32_t D, int64_t rows, int64_t r0, int
 // Launches outside an evaluation, under a footprint guard over ctx->A (with_B: and ctx->B as its
 // second region): a launch whose grid would leave them is not enqueued and the entry fails.
 template <typename Launches>
+int guarded_on(gaplac_ctx* ctx, const double* base, size_t elems, const double* base2, size_t elems2,
+               Launches&& launches);
+template <typename Launches>
 int guarded(gaplac_ctx* ctx, bool with_B, Launches&& launches) {
+    return guarded_on(ctx, ctx->A, ctx->A_elems, with_B ? ctx->B : nullptr, with_B ? ctx->B_elems : 0, launches);
+}
+// The same over any two allocations (the second may be null).
+template <typename Launches>
+int guarded_on(gaplac_ctx* ctx, const double* base, size_t elems, const double* base2, size_t elems2,
+               Launches&& launches) {
     LaunchGuard g;
-    g.base = ctx->A;
-    g.elems = (int64_t)ctx->A_elems;
-    if (with_B) {
-        g.base2 = ctx->B;
-        g.elems2 = (int64_t)ctx->B_elems;
+    g.base = base;
+    g.elems = (int64_t)elems;
+    if (base2) {
+        g.base2 = base2;
+        g.elems2 = (int64_t)elems2;
     }
     {
         GuardScope scope(&g);
@@ -1938,6 +1957,32 @@ SparseDims sparse_dims(int64_t N, int64_t Mz, int64_t Ms) {
     return d;
 }
 
+// The gradient's order-Mz scratch (§10.9): three column storages of Np columns, leading dimension
+// ld = 2 Np (a factor's copy above its identity rows), and the offsets of its vectors.
+struct SparseGradDims {
+    int nt;
+    int64_t Np, ld;
+    // vectors (doubles): u, c, -c, ctil, -ctil, zeros (Np each), the results, alpha (N)
+    int64_t u, c, nc, ct, nct, zero, out, alpha;
+};
+constexpr int64_t SG_OUT_UU = 0, SG_OUT_UF = GAPLAC_MAX_TERMS + 1, SG_OUT_TR = 2 * (GAPLAC_MAX_TERMS + 1);
+constexpr int64_t SG_OUT = 2 * (GAPLAC_MAX_TERMS + 1) + 2;
+SparseGradDims sparse_grad_dims(int64_t Mz) {
+    SparseGradDims g;
+    g.Np = round_up(Mz + 1, NB);
+    g.nt = (int)(g.Np / NB);
+    g.ld = 2 * g.Np;
+    g.u = 0;
+    g.c = g.Np;
+    g.nc = 2 * g.Np;
+    g.ct = 3 * g.Np;
+    g.nct = 4 * g.Np;
+    g.zero = 5 * g.Np;
+    g.out = 6 * g.Np;
+    g.alpha = 6 * g.Np + SG_OUT;
+    return g;
+}
+
 // The launches after an evaluation, run by the entries and walked dry by gaplac_plan_check_sparse
 // (the buffers besides A and B may be null there). Stage 2: the augmented matrix of S into B.
 void sparse_s_launches(hipStream_t s, const SparseDims& d, int64_t N, int64_t Mz, double* A, const double* y,
@@ -1991,6 +2036,15 @@ int sparse_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_
         });
     });
     if (rc) return rc;
+    if (ctx->sg_keep) {  // the gradient (§10.9): S before stage 3 factors it, Dinv before stage 3 reuses it
+        const SparseGradDims gd = sparse_grad_dims(Mz);
+        if ((rc = ensure(ctx, &ctx->sg, &ctx->sg_elems, (size_t)(3 * gd.ld * gd.Np)))) return rc;
+        if ((rc = ensure(ctx, &ctx->sg_dinv, &ctx->sg_dinv_elems, (size_t)gd.nt * DINV_PER_BLOCK))) return rc;
+        HIPCK(ctx, hipMemcpy2DAsync(ctx->sg + 2 * gd.ld * gd.Np, (size_t)gd.ld * 8, ctx->B, (size_t)d.ldb * 8,
+                                    (size_t)gd.Np * 8, (size_t)gd.Np, hipMemcpyDeviceToDevice, ctx->s_main));
+        HIPCK(ctx, hipMemcpyAsync(ctx->sg_dinv, ctx->Dinv, (size_t)gd.nt * DINV_PER_BLOCK * 8,
+                                  hipMemcpyDeviceToDevice, ctx->s_main));
+    }
     if (trace) {  // (stage 1 has retired: eval_device waited for it)
         std::vector<double> pv((size_t)N);
         HIPCK(ctx, hipMemcpy(pv.data(), ctx->pvar, (size_t)N * 8, hipMemcpyDeviceToHost));
@@ -2038,6 +2092,159 @@ int sparse_elbo_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int
     if (out_trace) *out_trace = trace;
     if (out_logdet) *out_logdet = logdet;
     if (out_quad) *out_quad = quad;
+    return 0;
+}
+
+// ---- gradient of the bound ----
+// The order-Mz launches, run by the entry under a guard over the scratch G and walked dry by
+// gaplac_plan_check_sparse_grad (the buffers besides G may be fake there). G1 = [L; I], G2 =
+// [L_S; I] and G3's top = S come in; G3's bottom = W', vec's c / ctil and the results leave.
+void sparse_grad_mz_launches(hipStream_t s, const SparseGradDims& g, int64_t Mz, double* G, const double* dinv1,
+                             const double* dinv2, double* vec, double* part, double noise, const double* Z,
+                             const TermPack* dtp, const GradTermPack* dgp, int T) {
+    const int64_t Np = g.Np, ld = g.ld;
+    double *G1 = G, *G2 = G + ld * Np, *G3 = G + 2 * ld * Np;
+    launch_init_identity_rows(s, G1, ld, Np, g.nt, g.nt);
+    launch_init_identity_rows(s, G2, ld, Np, g.nt, g.nt);
+    launch_rows_solve(s, G1, ld, g.nt, dinv1);  // Y1 = L^{-T}
+    launch_rows_solve(s, G2, ld, g.nt, dinv2);  // Y2 = L_S^{-T}
+    launch_zero_tail_cols(s, G1, ld, Np, Mz);
+    launch_zero_tail_cols(s, G2, ld, Np, Mz);
+    launch_copy_z(s, G2, ld, Mz, vec + g.u);                                              // u: L_S's v row
+    launch_alpha(s, G2, ld, Np, Mz, vec + g.u, part, vec + g.c, vec + g.nc);              // c = Y2 u
+    launch_alpha(s, G1, ld, Np, Mz, vec + g.c, part, vec + g.ct, vec + g.nct);            // ctil = Y1 c
+    launch_sg_nt(s, G2 + Np, ld, G2 + Np, ld, Np, true, true, G2, ld, Mz, 1.0, 1.0 / noise, 0.0, nullptr);  // Phi
+    launch_sg_nt(s, G1 + Np, ld, G2, ld, Np, true, false, G3 + Np, ld, Mz, -1.0, 0.0, 0.0, nullptr);       // W' = Y1 Phi
+    launch_sg_h(s, G3, G2, G2 + Np, ld, Np, Mz, noise, vec + g.out + SG_OUT_TR);                            // H, tr Phi
+    launch_sg_nt(s, G1 + Np, ld, G2 + Np, ld, Np, true, false, G1, ld, Mz, -1.0, 0.0, 0.0, nullptr);       // Y1 H
+    launch_sg_nt(s, G1, ld, G1 + Np, ld, Np, false, true, G3, ld, Mz, 0.5, 0.0, -0.5, vec + g.ct);         // G_uu
+    // sum G_uu o dKuu/dtheta (alpha = 0: the weights are G_uu alone); slot T: tr G_uu
+    launch_grad_contract(s, G3, ld, Mz, Z, Mz, vec + g.zero, dtp, dgp, part, nullptr);
+    const int m = (int)((Mz + NB - 1) / NB);
+    launch_grad_reduce(s, part, m * (m + 1) / 2, T, vec + g.out + SG_OUT_UU);
+}
+// The N-long launches, under a guard over the first workspace A and G: alpha, then the product.
+void sparse_grad_alpha_launches(hipStream_t s, const SparseDims& d, const SparseGradDims& g, int64_t N, int64_t Mz,
+                                const double* A, double* vec, double* part, double noise, const double* y) {
+    launch_sparse_alpha(s, A, d.lda, d.Np, Mz, N, vec + g.c, y, noise, part, vec + g.alpha);
+}
+void sparse_grad_uf_launches(hipStream_t s, const SparseDims& d, const SparseGradDims& g, int64_t N, int64_t Mz,
+                             const double* A, const double* G, double* vec, double* part, const double* X,
+                             const double* Z, const TermPack* dtp, const GradTermPack* dgp, bool groups, int T) {
+    launch_sparse_guf(s, A, d.lda, d.Np, N, Mz, G + 2 * g.ld * g.Np + g.Np, g.ld, X, N, Z, Mz, vec + g.alpha,
+                      vec + g.ct, dtp, dgp, groups, part);
+    launch_grad_reduce(s, part, (int)(((N + NB - 1) / NB) * ((Mz + NB - 1) / NB)), T, vec + g.out + SG_OUT_UF);
+}
+size_t sparse_grad_part_elems(int64_t N, int64_t Mz) {
+    const size_t nk = (size_t)((Mz + 511) / 512), m = (size_t)((Mz + NB - 1) / NB), mt = (size_t)((N + NB - 1) / NB);
+    const size_t S = GAPLAC_MAX_TERMS + 1;
+    return std::max(std::max(nk * (size_t)Mz, nk * (size_t)N), std::max(m * (m + 1) / 2 * S, mt * m * S));
+}
+
+// sum_n dk(x_n, x_n)/dtheta_t on the host (host_kdiag's loop): 1 for LINEAR's c and a NOISE
+// term's variance, 0 for a lengthscale (u = 0) and CAT, times the other terms of t's group.
+void host_dkdiag(const TermPack& tp, const GradTermPack& gp, const double* X, int64_t ldx, int64_t N, double* out) {
+    for (int t = 0; t < tp.T; ++t) {
+        out[t] = 0.0;
+        if (tp.kind[t] != GAPLAC_LINEAR && tp.kind[t] != GAPLAC_NOISE) continue;
+        for (int64_t n = 0; n < N; ++n) {
+            double d = 1.0;
+            for (int s = gp.gstart[t]; s < gp.gend[t]; ++s) {
+                if (s == t) continue;
+                const double x = tp.kind[s] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[s] * ldx + n];
+                if (tp.kind[s] == GAPLAC_LINEAR) d *= x * x + tp.p[s];
+                if (tp.kind[s] == GAPLAC_NOISE) d *= tp.p[s];
+            }
+            out[t] += d;
+        }
+    }
+}
+
+int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                          const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                          int64_t ldz, double jitter, double* out_elbo, double* out_dy, double* out_dparam,
+                          double* out_dnoise, double* out_djitter) {
+    if (!ctx) return GAPLAC_E_ARG;
+    for (double* o : {out_elbo, out_dnoise, out_djitter})
+        if (o) *o = NAN;
+    for (int t = 0; out_dparam && t < T && t < GAPLAC_MAX_TERMS; ++t) out_dparam[t] = NAN;
+    for (int64_t n = 0; out_dy && n < N; ++n) out_dy[n] = NAN;
+    // the value, by its own schedule; with sg_keep its stages leave S and the first Dinv behind
+    struct Keep {
+        gaplac_ctx* c;
+        explicit Keep(gaplac_ctx* ctx) : c(ctx) { c->sg_keep = true; }
+        ~Keep() { c->sg_keep = false; }
+    } keep(ctx);
+    if (!out_elbo) return set_err(ctx, GAPLAC_E_ARG, "out_elbo is NULL");
+    double elbo = NAN, trace = NAN;
+    int rc = sparse_elbo_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, &elbo, nullptr, &trace, nullptr,
+                              nullptr);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    GradTermPack gp{};
+    for (int t = 0; t < T; ++t) {
+        int a = t, b = t + 1;
+        while (a > 0 && terms[a - 1].group == terms[t].group) --a;
+        while (b < T && terms[b].group == terms[t].group) ++b;
+        gp.gstart[t] = a;
+        gp.gend[t] = b;
+    }
+    bool groups = false;
+    for (int t = 0; t < T; ++t) groups = groups || gp.gend[t] - gp.gstart[t] > 1;
+    double dsum[GAPLAC_MAX_TERMS + 1] = {};
+    host_dkdiag(tp, gp, X, ldx, N, dsum);
+    std::vector<double> alpha((size_t)std::max<int64_t>(N, 0));
+    double outs[SG_OUT] = {};
+    if (N > 0 && Mz == 0) {  // Q = 0: alpha = y / noise, no inducing pieces
+        for (int64_t n = 0; n < N; ++n) alpha[(size_t)n] = y[n] / noise;
+    } else if (N > 0) {
+        const SparseDims d = sparse_dims(N, Mz, 0);
+        const SparseGradDims g = sparse_grad_dims(Mz);
+        HIPCK(ctx, hipSetDevice(ctx->device));
+        if ((rc = ensure(ctx, &ctx->sg_v, &ctx->sg_v_elems, (size_t)(g.alpha + N)))) return rc;
+        if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, sparse_grad_part_elems(N, Mz)))) return rc;
+        // (the value has retired: ctx->A is the first workspace again, L above V^T; ctx->B holds L_S,
+        // ctx->Dinv its inverses, ctx->dX = Z, ctx->dXs = X, ctx->dtp the pack)
+        double* const G = ctx->sg;
+        HIPCK(ctx, hipMemcpy2DAsync(G, (size_t)g.ld * 8, ctx->A, (size_t)d.lda * 8, (size_t)g.Np * 8, (size_t)g.Np,
+                                    hipMemcpyDeviceToDevice, ctx->s_main));
+        HIPCK(ctx, hipMemcpy2DAsync(G + g.ld * g.Np, (size_t)g.ld * 8, ctx->B, (size_t)d.ldb * 8, (size_t)g.Np * 8,
+                                    (size_t)g.Np, hipMemcpyDeviceToDevice, ctx->s_main));
+        HIPCK(ctx, hipMemsetAsync(ctx->sg_v + g.zero, 0, (size_t)g.Np * 8, ctx->s_main));
+        *ctx->hgp = gp;
+        HIPCK(ctx, hipMemcpyAsync(ctx->dgp, ctx->hgp, sizeof(GradTermPack), hipMemcpyHostToDevice, ctx->s_main));
+        if ((rc = guarded_on(ctx, G, ctx->sg_elems, nullptr, 0, [&] {
+                 sparse_grad_mz_launches(ctx->s_main, g, Mz, G, ctx->sg_dinv, ctx->Dinv, ctx->sg_v, ctx->gpart, noise,
+                                         ctx->dX, ctx->dtp, ctx->dgp, T);
+             })))
+            return rc;
+        if ((rc = guarded_on(ctx, ctx->A, ctx->A_elems, G, ctx->sg_elems, [&] {
+                 sparse_grad_alpha_launches(ctx->s_main, d, g, N, Mz, ctx->A, ctx->sg_v, ctx->gpart, noise, ctx->sp_y);
+             })))
+            return rc;
+        // <trace path>.sg: "N Mz ms" of the product kernel (and its reduction) alone
+        rc = trace_timed(ctx, ".sg", N, Mz, [&] {
+            return guarded_on(ctx, ctx->A, ctx->A_elems, G, ctx->sg_elems, [&] {
+                sparse_grad_uf_launches(ctx->s_main, d, g, N, Mz, ctx->A, G, ctx->sg_v, ctx->gpart, ctx->dXs, ctx->dX,
+                                        ctx->dtp, ctx->dgp, groups, T);
+            });
+        });
+        if (rc) return rc;
+        HIPCK(ctx, hipMemcpyAsync(alpha.data(), ctx->sg_v + g.alpha, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->s_main));
+        HIPCK(ctx, hipMemcpyAsync(outs, ctx->sg_v + g.out, sizeof outs, hipMemcpyDeviceToHost, ctx->s_main));
+        HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    }
+    double ata = 0.0;
+    for (int64_t n = 0; n < N; ++n) ata += alpha[(size_t)n] * alpha[(size_t)n];
+    if (out_elbo) *out_elbo = elbo;
+    for (int64_t n = 0; out_dy && n < N; ++n) out_dy[n] = -alpha[(size_t)n];
+    for (int t = 0; out_dparam && t < T; ++t)
+        out_dparam[t] = N > 0 ? -dsum[t] / (2.0 * noise) + 2.0 * outs[SG_OUT_UF + t] + 2.0 * outs[SG_OUT_UU + t] : 0.0;
+    // (N - Mz + noise tr S^{-1}) / noise = N / noise - tr Phi
+    if (out_dnoise)
+        *out_dnoise = N > 0 ? 0.5 * (ata - ((double)N / noise - outs[SG_OUT_TR])) + trace / (2.0 * noise * noise) : 0.0;
+    if (out_djitter) *out_djitter = N > 0 ? 2.0 * outs[SG_OUT_UU + T] : 0.0;
     return 0;
 }
 
@@ -2750,6 +2957,14 @@ int gaplac_sparse_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, cons
                                  out_var);
 }
 
+int gaplac_sparse_elbo_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                            const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                            int64_t ldz, double jitter, double* out_elbo, double* out_dy, double* out_dparam,
+                            double* out_dnoise, double* out_djitter) {
+    return sparse_elbo_grad_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, out_elbo, out_dy,
+                                 out_dparam, out_dnoise, out_djitter);
+}
+
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {
     if (N < 0 || Mz < 0 || !out_chunks || !out_chunk_rows) return GAPLAC_E_ARG;
     sparse_split(N, Mz, out_chunks, out_chunk_rows);
@@ -2803,6 +3018,47 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
     const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.violations ? g3.first : g4.first;
     if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
     return rc;
+}
+
+// Host-only walk of gaplac_sparse_elbo_grad: the three stages of the value (gaplac_plan_check_sparse
+// at Ms = 0), then the gradient's own launches run dry: the order-Mz launches against the
+// scratch, the N-long launches (alpha, the product kernel) against the first workspace and the
+// scratch as its second region. short_ws 1: the first workspace one element short (the value's
+// walk and the product kernel's riding rows both leave it); 2: the second workspace of the value
+// and the gradient's scratch one element short (negative controls).
+int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                                  int64_t* out_violations, char* msg, int64_t msglen) {
+    int64_t l0 = 0, v0 = 0;
+    int rc = gaplac_plan_check_sparse(N, Mz, 0, spw, short_ws, &l0, &v0, msg, msglen);
+    if (rc) return rc;
+    const SparseDims d = sparse_dims(N, Mz, 0);
+    const SparseGradDims g = sparse_grad_dims(Mz);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fg = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    double* const fv = reinterpret_cast<double*>((uintptr_t)1 << 46);  // vectors, partials, Dinv: never guarded
+    LaunchGuard g1, g2;
+    g1.base = fg;
+    g1.elems = 3 * g.ld * g.Np - (short_ws == 2 ? 1 : 0);
+    g1.dry = true;
+    g2.base = fa;
+    g2.elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0);
+    g2.base2 = fg;
+    g2.elems2 = g1.elems;
+    g2.dry = true;
+    {
+        GuardScope scope(&g1);
+        sparse_grad_mz_launches(nullptr, g, Mz, fg, fv, fv, fv, fv, 1.0, nullptr, nullptr, nullptr, 1);
+    }
+    {
+        GuardScope scope(&g2);
+        sparse_grad_alpha_launches(nullptr, d, g, N, Mz, fa, fv, fv, 1.0, nullptr);
+        sparse_grad_uf_launches(nullptr, d, g, N, Mz, fa, fg, fv, fv, nullptr, nullptr, nullptr, nullptr, false, 1);
+    }
+    if (out_launches) *out_launches = l0 + g1.launches + g2.launches;
+    if (out_violations) *out_violations = v0 + g1.violations + g2.violations;
+    if (msg && msglen > 0 && v0 == 0 && (g1.violations || g2.violations))
+        std::snprintf(msg, (size_t)msglen, "%s", (g1.violations ? g1.first : g2.first).c_str());
+    return 0;
 }
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior

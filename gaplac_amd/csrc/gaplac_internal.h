@@ -364,6 +364,33 @@ void launch_rows_to_matrix(hipStream_t s, const double* A, int64_t lda, int64_t 
 // row): mean_j = c_j . u, var_j += noise |c_j|^2 (partial: 2 * ceil(Mz/512) * Ms doubles).
 void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t Ms, double noise,
                         double* partial, double* mean, double* var);
+// ---- gradient of the inducing-point bound ----
+// G: a column storage of nt tile columns (leading dimension ld >= 2 nt 128) holding a factor in
+// tile rows 0 .. nt-1 and identity rows (launch_init_identity_rows, W = nt) in tile rows nt ..
+// 2 nt - 1; Dinv the factorisation's inverses. Leaves Y = L^{-T} (upper triangular) in the rows:
+// per column the substitution of launch_trsm_rows, then its update of the later columns
+// (K = 128), the single-super-panel form of the gradient's extra-row chain.
+void launch_rows_solve(hipStream_t s, double* G, int64_t ld, int nt, const double* Dinv);
+// C = sa * (-P Q^T) + sd * I + sv * v v^T (v or nullptr), all Np x Np tiles, zero outside order
+// Mz: P, Q, C row blocks of column storages in one guarded scratch (P[i, k] = P[k ldp + i], the
+// sum over k < Np). pu / qu: P / Q is upper triangular (the sum starts at the tile's diagonal).
+void launch_sg_nt(hipStream_t s, const double* P, int64_t ldp, const double* Q, int64_t ldq, int64_t Np, bool pu,
+                  bool qu, double* C, int64_t ldc, int64_t Mz, double sa, double sd, double sv, const double* v);
+// H = S / noise - I - noise Phi (S from its lower triangle), and tr_phi[0] = tr Phi.
+void launch_sg_h(hipStream_t s, const double* S, const double* Phi, double* H, int64_t ld, int64_t Np, int64_t Mz,
+                 double noise, double* tr_phi);
+// alpha = (y - V^T c) / noise over the N riding rows of the first evaluation (partial:
+// ceil(Mz/512) * N doubles), fixed order.
+void launch_sparse_alpha(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t N,
+                         const double* c, const double* y, double noise, double* partial, double* alpha);
+// Per 128x128 tile of G_uf^T = alpha ctil^T + V^T W'^T (rows n < N of the riding rows of A,
+// columns m < Mz of W', a row block with leading dimension ldw in the guard's second
+// allocation), never stored: partial[(tile row * ceil(Mz/128) + tile column) (T + 1) + t] = its
+// sum with dk(z_m, x_n)/dtheta_t (launch_grad_reduce's layout; slot T is 0). X: the rows'
+// coordinates (ld ldx), Z: the columns'. groups: the formula has product groups (the slower kernel).
+void launch_sparse_guf(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t Mz, const double* W,
+                       int64_t ldw, const double* X, int64_t ldx, const double* Z, int64_t ldz, const double* alpha,
+                       const double* ctil, const TermPack* dtp, const GradTermPack* dgp, bool groups, double* partial);
 // O[:, c] += mean, c < R (O is M x R, leading dimension ldo).
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean);
 // After the factorisation and launch_reduce (same stream): quad_r = sum_k W^T[r,k]^2 and

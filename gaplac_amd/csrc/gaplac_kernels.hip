@@ -1422,8 +1422,9 @@ static_assert(sizeof(MmaLds) >= GRAM_LDS * sizeof(double), "gram_tile reuses the
 template <int KBT = KB>
 __device__ __forceinline__ void tile_mma_neg(const double* __restrict__ P, const double* __restrict__ Q,
                                              int64_t ldp, int kdepth, bool active, d4 (&acc)[4][4],
-                                             MmaLdsT<KBT>& sm) {
+                                             MmaLdsT<KBT>& sm, int64_t ldq = 0) {
     constexpr int KB = KBT;
+    const int64_t lq = ldq ? ldq : ldp;  // Q in a storage of its own (the sparse gradient's W'); 0: P's
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
     const int wi = w & 1, wj = w >> 1;
@@ -1439,7 +1440,7 @@ __device__ __forceinline__ void tile_mma_neg(const double* __restrict__ P, const
 #pragma unroll
         for (int it = 0; it < 2 * KB / 4; ++it) {
             const int t = w + 4 * it, o = t / KB, r = t % KB;
-            const double* src = (o ? Q : P) + (int64_t)(ch * KB + r) * ldp + 2 * lane;
+            const double* src = (o ? Q : P) + (int64_t)(ch * KB + r) * (o ? lq : ldp) + 2 * lane;
             __builtin_amdgcn_global_load_lds((GlobalCPtr)src, (LdsPtr)&sm[buf][o][r][0], 16, 0, 0);
         }
     };
@@ -2931,6 +2932,296 @@ __global__ __launch_bounds__(256) void sparse_post_finish_kernel(const double* _
     var[j] = var[j] + noise * v;
 }
 
+// ---------------------------------------------------------------------------------
+// Gradient of the inducing-point bound. With V^T still below the first
+// factor and L_S in the second workspace:
+//   c = L_S^{-T} u, ctil = L^{-T} c, alpha = (y - V^T c) / noise, Phi = I / noise - S^{-1},
+//   W' = L^{-T} Phi, G_uf = ctil alpha^T + W' V, G_uu = -1/2 (ctil ctil^T + L^{-T} H L^{-1}),
+//   H = S / noise - 2 I + noise S^{-1} = S / noise - I - noise Phi.
+// The order-Mz pieces live in a scratch of three column storages (Np columns, leading dimension
+// 2 Np each): copies of the two factors with identity rows below them, solved column by
+// column with the factorisation's own substitution and update kernels (Y = L^{-T}, upper
+// triangular), then four tile products of the form P Q^T over the storages' columns. The
+// N-long work is alpha (a GEMV over V^T) and sparse_guf_kernel: the product W' V, never stored.
+// ---------------------------------------------------------------------------------
+
+// One 128x128 tile (blockIdx.x, blockIdx.y) of C = sa * (-P Q^T) + sd * I + sv * v v^T over the
+// Np columns k of P and Q (row blocks of column storages: P[i, k] = P[k ldp + i]), zero
+// outside i, j < Mz. pu / qu: P / Q is upper triangular in (row, k), so the sum starts at the
+// tile's first possibly nonzero column (the skipped products are exact zeros). tile_mma_neg's
+// chain, one accumulator per element in ascending k.
+__global__ __launch_bounds__(256, 2) void sg_nt_kernel(const double* __restrict__ P, int64_t ldp,
+                                                       const double* __restrict__ Q, int64_t ldq, int64_t Np,
+                                                       int pu, int qu, double* __restrict__ C, int64_t ldc,
+                                                       int64_t Mz, double sa, double sd, double sv,
+                                                       const double* __restrict__ v) {
+    __shared__ MmaLds sm;
+    const int bi = (int)blockIdx.x, bj = (int)blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wi = w & 1, wj = w >> 1;
+    const int fr = lane >> 4, fc = lane & 15;
+    int kb = 0;
+    if (pu) kb = bi;
+    if (qu && bj > kb) kb = bj;
+    const int64_t k0 = (int64_t)kb * NB;
+    d4 acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj) acc[mi][mj] = d4{0.0, 0.0, 0.0, 0.0};
+    tile_mma_neg(P + k0 * ldp + (int64_t)bi * NB, Q + k0 * ldq + (int64_t)bj * NB, ldp, (int)(Np - k0), true, acc, sm,
+                 ldq);
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int64_t i = (int64_t)bi * NB + 64 * wi + 16 * mi + fc;
+        const double vi = (v && i < Mz) ? v[i] : 0.0;
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int64_t j = (int64_t)bj * NB + 64 * wj + 16 * mj + fr + 4 * rg;
+                const double vj = (v && j < Mz) ? v[j] : 0.0;
+                double x = sa * acc[mi][mj][rg] + sv * (vi * vj);
+                if (i == j) x += sd;
+                C[j * ldc + i] = (i < Mz && j < Mz) ? x : 0.0;
+            }
+    }
+}
+
+// H = S / noise - I - noise Phi (order Mz, zero outside), S read from its lower triangle (the
+// saved matrix of stage 2 holds its lower tiles only). blockIdx.y is the column.
+__global__ __launch_bounds__(256) void sg_h_kernel(const double* __restrict__ S, const double* __restrict__ Phi,
+                                                   double* __restrict__ H, int64_t ld, int64_t Np, int64_t Mz,
+                                                   double noise) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = blockIdx.y;
+    if (i >= Np) return;
+    double h = 0.0;
+    if (i < Mz && j < Mz) {
+        const double s = i >= j ? S[j * ld + i] : S[i * ld + j];
+        h = s / noise - noise * Phi[j * ld + i];
+        if (i == j) h -= 1.0;
+    }
+    H[j * ld + i] = h;
+}
+
+// out[0] = sum_i M[i, i], i < n: one workgroup, a fixed tree.
+__global__ __launch_bounds__(256) void sg_trace_kernel(const double* __restrict__ M, int64_t ld, int64_t n,
+                                                       double* __restrict__ out) {
+    __shared__ double s[256];
+    const int tid = threadIdx.x;
+    double x = 0.0;
+    for (int64_t i = tid; i < n; i += 256) x += M[i * ld + i];
+    s[tid] = x;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s[tid] += s[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = s[0];
+}
+
+// Partial sums of V^T c over 512-column chunks of the riding rows (alpha_partial_kernel's
+// shape): block (x, y) = rows 256 x .., columns 512 y ..
+__global__ __launch_bounds__(256) void sparse_alpha_partial_kernel(const double* __restrict__ A, int64_t lda,
+                                                                   int64_t Np, int64_t Mz, int64_t N,
+                                                                   const double* __restrict__ c,
+                                                                   double* __restrict__ pm) {
+    __shared__ double cs[512];
+    const int tid = threadIdx.x;
+    const int64_t k0 = (int64_t)blockIdx.y * 512;
+    const int64_t n = (int64_t)blockIdx.x * 256 + tid;
+    for (int t = tid; t < 512; t += 256) cs[t] = (k0 + t < Mz) ? c[k0 + t] : 0.0;
+    __syncthreads();
+    if (n >= N) return;
+    const double* r = A + k0 * lda + Np + n;
+    const int kn = (int)((Mz - k0) < 512 ? (Mz - k0) : 512);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int kk = 0;
+    for (; kk + 4 <= kn; kk += 4) {
+        s0 += r[(int64_t)kk * lda] * cs[kk];
+        s1 += r[(int64_t)(kk + 1) * lda] * cs[kk + 1];
+        s2 += r[(int64_t)(kk + 2) * lda] * cs[kk + 2];
+        s3 += r[(int64_t)(kk + 3) * lda] * cs[kk + 3];
+    }
+    for (; kk < kn; ++kk) s0 += r[(int64_t)kk * lda] * cs[kk];
+    pm[(int64_t)blockIdx.y * N + n] = (s0 + s1) + (s2 + s3);
+}
+
+// alpha_n = (y_n - sum of the partials in chunk order) / noise
+__global__ __launch_bounds__(256) void sparse_alpha_finish_kernel(const double* __restrict__ pm, int64_t N, int nk,
+                                                                  const double* __restrict__ y, double noise,
+                                                                  double* __restrict__ alpha) {
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    double a = 0.0;
+    for (int q = 0; q < nk; ++q) a += pm[(int64_t)q * N + n];
+    alpha[n] = (y[n] - a) / noise;
+}
+
+// One 128x128 tile of G_uf^T: rows n of X (tile row blockIdx.y of the riding rows), columns m
+// of Z (tile column blockIdx.x): sum_k V^T[n, k] W'[m, k] over the Np columns of the two
+// storages (V^T's column Mz holds y and W' zeros there and beyond), tile_mma_neg's chain, then
+// in registers the weight alpha_n ctil_m + (W' V)[m, n] (0 for n >= N, the rows of the padding,
+// and m >= Mz) contracted with dk(z_m, x_n)/dtheta_t for every term: cinv_contract_kernel's
+// epilogue on a rectangle (every element counts once, no diagonal: a NOISE term is 0 across
+// point sets), a run-time loop over the terms. partial[(blockIdx.y gridDim.x + blockIdx.x) (T +
+// 1) + t], t < T; slot T is 0. GROUPS: terms inside product groups carry the group's other
+// terms (term_k's arithmetic, a second set of 64 weights: the slower path); without it such a
+// term's slot is not meaningful and the host never launches that variant for such a formula.
+template <bool GROUPS>
+__device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                const double* __restrict__ W, int64_t ldw, int64_t N, int64_t Mz,
+                                                const double* __restrict__ X, int64_t ldx,
+                                                const double* __restrict__ Z, int64_t ldz,
+                                                const double* __restrict__ alpha, const double* __restrict__ ctil,
+                                                const TermPack* __restrict__ tpp,
+                                                const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
+    __shared__ MmaLds sm;
+    const int bm = (int)blockIdx.x, bn = (int)blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int wi = w & 1, wj = w >> 1;
+    const int fr = lane >> 4, fc = lane & 15;
+    d4 acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj) acc[mi][mj] = d4{0.0, 0.0, 0.0, 0.0};
+    tile_mma_neg(A + Np + (int64_t)bn * NB, W + (int64_t)bm * NB, lda, (int)Np, true, acc, sm, ldw);
+    // (tile_mma_neg ends on a barrier: the staging buffer is free)
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    double* const xr = &sm[0][0][0][0];             // xr[t * 128 + r]: coordinates of the rows (X)
+    double* const xc = xr + GAPLAC_MAX_TERMS * NB;  // xc[t * 128 + c]: of the columns (Z)
+    double* const ar = xc + GAPLAC_MAX_TERMS * NB;  // alpha of the rows
+    double* const ac = ar + NB;                     // ctil of the columns
+    double* const tbl = ac + NB;                    // exp table
+#if GAPLAC_KB == 16
+    double* const red = tbl + 256;  // red[w * (T + 1) + t]
+#else
+    __shared__ double red[4 * (GAPLAC_MAX_TERMS + 1)];
+#endif
+    const int64_t r0 = (int64_t)bn * NB, c0 = (int64_t)bm * NB;
+    for (int idx = tid; idx < T * NB; idx += 256) {
+        const int t = idx / NB, q = idx % NB;
+        const bool x = tp.kind[t] != GAPLAC_NOISE;
+        xr[t * NB + q] = (x && r0 + q < N) ? X[(int64_t)tp.col[t] * ldx + r0 + q] : 0.0;
+        xc[t * NB + q] = (x && c0 + q < Mz) ? Z[(int64_t)tp.col[t] * ldz + c0 + q] : 0.0;
+    }
+    if (tid < NB) {
+        ar[tid] = r0 + tid < N ? alpha[r0 + tid] : 0.0;
+        ac[tid] = c0 + tid < Mz ? ctil[c0 + tid] : 0.0;
+    }
+    tbl[tid] = kExp2Tbl256[tid];
+    __syncthreads();
+    // weights in place (the chain left -(W' V))
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int rr = 64 * wi + 16 * mi + fc;
+        const bool rin = r0 + rr < N;
+        const double ai = ar[rr];
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg) {
+                const int cc = 64 * wj + 16 * mj + fr + 4 * rg;
+                const bool in = rin && c0 + cc < Mz;
+                acc[mi][mj][rg] = in ? (ai * ac[cc] - acc[mi][mj][rg]) : 0.0;
+            }
+    }
+#pragma unroll 1
+    for (int t = 0; t <= T; ++t) {
+        double g = 0.0;
+        const int kind = t < T ? tp.kind[t] : GAPLAC_CAT;  // (slot T: nothing)
+        const int gs = t < T ? gpp->gstart[t] : 0, ge = t < T ? gpp->gend[t] : 1;
+        if (GROUPS && ge - gs > 1) {
+            const double p = tp.p[t];
+            d4 wm[4][4];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj) wm[mi][mj] = acc[mi][mj];
+#pragma unroll 1
+            for (int s2 = gs; s2 < ge; ++s2) {
+                if (s2 == t) continue;
+                const int k2 = tp.kind[s2];
+                const double p2 = tp.p[s2];
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) {
+                    const double xi = xr[s2 * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                    for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                        for (int rg = 0; rg < 4; ++rg)
+                            wm[mi][mj][rg] *= term_k(k2, p2, xi, xc[s2 * NB + 64 * wj + 16 * mj + fr + 4 * rg], false);
+                }
+            }
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const double xi = xr[t * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg)
+                        g += wm[mi][mj][rg] * term_dk(kind, p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], false);
+            }
+        } else if (kind == GAPLAC_SQEXP) {
+            const double p = tp.p[t];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const double xi = xr[t * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg)
+                        g += acc[mi][mj][rg] * dk_sqexp(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+            }
+        } else if (kind == GAPLAC_OU) {
+            const double p = tp.p[t];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const double xi = xr[t * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg)
+                        g += acc[mi][mj][rg] * dk_ou(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+            }
+        } else if (kind == GAPLAC_LINEAR) {  // d/dc (x z + c) = 1
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg) g += acc[mi][mj][rg];
+        }  // Cat: no parameter; Noise: 0 across point sets
+        const double x = wave_sum(g);
+        if (lane == 0) red[w * (T + 1) + t] = x;
+    }
+    __syncthreads();
+    if (tid <= T) {
+        const int64_t b = (int64_t)bn * gridDim.x + bm;
+        const int S = T + 1;
+        partial[b * S + tid] = (red[tid] + red[S + tid]) + (red[2 * S + tid] + red[3 * S + tid]);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void sparse_guf_kernel(
+    const double* __restrict__ A, int64_t lda, int64_t Np, const double* __restrict__ W, int64_t ldw, int64_t N,
+    int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
+    const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
+    const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
+    sparse_guf_body<false>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial);
+}
+// (one workgroup per CU: the second set of weights takes the registers of a second workgroup)
+__global__ __launch_bounds__(256) void sparse_guf_groups_kernel(
+    const double* __restrict__ A, int64_t lda, int64_t Np, const double* __restrict__ W, int64_t ldw, int64_t N,
+    int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
+    const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
+    const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
+    sparse_guf_body<true>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial);
+}
+
 // =================================================================================
 // Persistent tail: the last T <= TAIL_TMAX tile columns ts .. nt-1
 // of the factorisation in ONE launch, as a dataflow of tile tasks instead of per-column
@@ -4285,6 +4576,72 @@ void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np,
                                                                                              pv);
     sparse_post_finish_kernel<<<dim3((unsigned)((Ms + 255) / 256)), dim3(256), 0, s>>>(pm, pv, Ms, nk, noise, mean,
                                                                                       var);
+}
+
+void launch_rows_solve(hipStream_t s, double* G, int64_t ld, int nt, const double* Dinv) {
+    for (int c = 0; c < nt; ++c) {
+        double* Gcol = G + (int64_t)c * NB * ld;
+        if (c > 0) {  // column c - 1 of the rows applied to the columns from c on (rows 0 .. c-1 are nonzero)
+            BulkArgs ba{G, ld, Panel{Gcol - NB * ld, ld, 0}, nullptr, c * (nt - c), NB, nt, c, ColMap{1, 0, nt}};
+            ba.rect_rows = c;
+            ba.tile_min = 128;
+            launch_bulk(s, ba, nullptr);
+        }
+        launch_trsm_rows(s, Gcol, ld, c, nt, c + 1, Dinv + (size_t)c * DINV_PER_BLOCK, nullptr);
+    }
+}
+
+void launch_sg_nt(hipStream_t s, const double* P, int64_t ldp, const double* Q, int64_t ldq, int64_t Np, bool pu,
+                  bool qu, double* C, int64_t ldc, int64_t Mz, double sa, double sd, double sv, const double* v) {
+    if (Np <= 0) return;
+    // reads rows < Np of every column of P and Q, writes rows < Np of every column of C (one scratch)
+    const bool p_ok = guard_launch("sg_nt_kernel (P)", P, 0, (Np - 1) * ldp + Np);
+    const bool q_ok = guard_launch("sg_nt_kernel (Q)", Q, 0, (Np - 1) * ldq + Np);
+    const bool c_ok = guard_launch("sg_nt_kernel", C, 0, (Np - 1) * ldc + Np);
+    if (!p_ok || !q_ok || !c_ok) return;
+    const unsigned nb = (unsigned)(Np / NB);
+    sg_nt_kernel<<<dim3(nb, nb), dim3(256), 0, s>>>(P, ldp, Q, ldq, Np, pu ? 1 : 0, qu ? 1 : 0, C, ldc, Mz, sa, sd,
+                                                    sv, v);
+}
+
+void launch_sg_h(hipStream_t s, const double* S, const double* Phi, double* H, int64_t ld, int64_t Np, int64_t Mz,
+                 double noise, double* tr_phi) {
+    if (Np <= 0) return;
+    const bool s_ok = guard_launch("sg_h_kernel (S)", S, 0, (Np - 1) * ld + Np);
+    const bool p_ok = guard_launch("sg_h_kernel (Phi)", Phi, 0, (Np - 1) * ld + Np);
+    const bool h_ok = guard_launch("sg_h_kernel", H, 0, (Np - 1) * ld + Np);
+    if (!s_ok || !p_ok || !h_ok) return;
+    sg_h_kernel<<<dim3((unsigned)((Np + 255) / 256), (unsigned)Np), dim3(256), 0, s>>>(S, Phi, H, ld, Np, Mz, noise);
+    sg_trace_kernel<<<dim3(1), dim3(256), 0, s>>>(Phi, ld, Mz, tr_phi);
+}
+
+void launch_sparse_alpha(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t N,
+                         const double* c, const double* y, double noise, double* partial, double* alpha) {
+    if (Mz <= 0 || N <= 0) return;
+    if (!guard_launch("sparse_alpha_partial_kernel", A, Np, (Mz - 1) * lda + Np + N)) return;
+    const int nk = (int)((Mz + 511) / 512);
+    sparse_alpha_partial_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)nk), dim3(256), 0, s>>>(A, lda, Np, Mz,
+                                                                                                    N, c, partial);
+    sparse_alpha_finish_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(partial, N, nk, y, noise, alpha);
+}
+
+void launch_sparse_guf(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t Mz, const double* W,
+                       int64_t ldw, const double* X, int64_t ldx, const double* Z, int64_t ldz, const double* alpha,
+                       const double* ctil, const TermPack* dtp, const GradTermPack* dgp, bool groups,
+                       double* partial) {
+    if (Mz <= 0 || N <= 0) return;
+    const int64_t mt = (N + NB - 1) / NB, ntm = (Mz + NB - 1) / NB;
+    // reads the mt tile rows of riding rows of every column of A, and rows < ntm 128 of every column of W
+    const bool a_ok = guard_launch("sparse_guf_kernel (riding rows)", A, Np, (Np - 1) * lda + Np + mt * NB);
+    const bool w_ok = guard_launch("sparse_guf_kernel (W')", W, 0, (Np - 1) * ldw + ntm * NB, 1);
+    if (!a_ok || !w_ok) return;
+    const dim3 grid((unsigned)ntm, (unsigned)mt);
+    if (groups)
+        sparse_guf_groups_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, dtp,
+                                                            dgp, partial);
+    else
+        sparse_guf_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, dtp, dgp,
+                                                     partial);
 }
 
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean) {

@@ -53,20 +53,28 @@ class GradMemo:
         self.key = None
         self.X = None
         self.v = None
+        self.Z = None
         self.val = None
         self.calls = 0
 
-    def __call__(self, ctx, X, terms, noise: float, v):
+    def __call__(self, ctx, X, terms, noise: float, v, Z=None, jitter: float = 0.0):
         # keyed on the VALUES of X and v (copies kept and compared), never on a buffer
-        # address: an X modified in place, or a new X in a reused buffer, misses the memo
+        # address: an X modified in place, or a new X in a reused buffer, misses the memo.
+        # With inducing inputs Z the call is gaplac_sparse_elbo_grad and Z and jitter are part
+        # of the key; the value is then (elbo, dy, dparam, dnoise, djitter).
         X = np.ascontiguousarray(X, dtype=np.float64)
         v = np.ascontiguousarray(v, dtype=np.float64)
-        key = (X.shape, tuple(map(tuple, terms)), float(noise))
+        Z = None if Z is None else np.ascontiguousarray(Z, dtype=np.float64)
+        key = (X.shape, tuple(map(tuple, terms)), float(noise), None if Z is None else (Z.shape, float(jitter)))
         hit = (key == self.key and self.v is not None and np.array_equal(v, self.v)
-               and np.array_equal(X, self.X))
+               and np.array_equal(X, self.X) and (Z is None or np.array_equal(Z, self.Z)))
         if not hit:
-            self.val = ctx.logpdf_grad(X, terms, noise, v)
+            if Z is None:
+                self.val = ctx.logpdf_grad(X, terms, noise, v)
+            else:
+                self.val = ctx.sparse_elbo_grad(X, terms, noise, v, Z, jitter)
             self.key, self.X, self.v = key, X.copy(), v.copy()
+            self.Z = None if Z is None else Z.copy()
             self.calls += 1
         return self.val
 
@@ -74,7 +82,8 @@ class GradMemo:
 class MCMCModel:
     """inference_engine(y, x, formula, inferable) of CLI/src/mcmc.jl:31-39 on a table."""
 
-    def __init__(self, formula: str, table, infer, ctx: backend.Context | None = None):
+    def __init__(self, formula: str, table, infer, ctx: backend.Context | None = None, inducing=None,
+                 jitter: float = 1e-6):
         spec = F.gp_spec(formula)                       # mcmc.jl:14
         self.formula = F.formula(spec)
         _, vars_ = AG.make_gp(spec)                     # mcmc.jl:19
@@ -84,6 +93,15 @@ class MCMCModel:
         self.X = AG.design_matrix(table, vars_)         # mcmc.jl:26 Matrix(df[!, vars])
         self.ctx = ctx
         self.memo = GradMemo()
+        # inducing inputs (Mz x D, the design matrix's columns): the GP term becomes the VFE bound
+        # elbo(VFE(f(Z, jitter)), f(X, 0.1), fx) and its gradient (one gaplac_sparse_elbo_grad call)
+        self.inducing = None
+        self.jitter = float(jitter)
+        if inducing is not None:
+            Z = np.asarray(inducing, dtype=np.float64)
+            if Z.ndim != 2 or Z.shape[1] != self.X.shape[1]:
+                raise F.ArgumentError("DimensionMismatch: inducing inputs need the design matrix's columns")
+            self.inducing = Z
 
     @property
     def N(self) -> int:
@@ -116,7 +134,10 @@ class MCMCModel:
             return -math.inf, math.nan, np.full(self.N, math.nan)
         terms = self.terms(ell)
         ctx = self.ctx or backend.default_context()
-        lp_gp, dv, dparam, _ = self.memo(ctx, self.X, terms, NOISE_VAR, fx)
+        if self.inducing is None:
+            lp_gp, dv, dparam, _ = self.memo(ctx, self.X, terms, NOISE_VAR, fx)
+        else:
+            lp_gp, dv, dparam, _, _ = self.memo(ctx, self.X, terms, NOISE_VAR, fx, self.inducing, self.jitter)
         r = self.y - fx
         lik = float(np.sum(-(LOG2PI + r * r) / 2))
         prior = -math.log(ELL_HI - ELL_LO)
@@ -124,12 +145,15 @@ class MCMCModel:
         return prior + lp_gp + lik, dell, dv + r
 
     def logdensity(self, ell: float, fx) -> float:
-        """The log joint alone (one gaplac_logpdf call)."""
+        """The log joint alone (one gaplac_logpdf call; with inducing inputs one gaplac_sparse_elbo)."""
         fx = np.asarray(fx, dtype=np.float64)
         if not (ELL_LO <= ell <= ELL_HI):
             return -math.inf
         ctx = self.ctx or backend.default_context()
-        lp_gp = ctx.logpdf(self.X, self.terms(ell), NOISE_VAR, fx)
+        if self.inducing is None:
+            lp_gp = ctx.logpdf(self.X, self.terms(ell), NOISE_VAR, fx)
+        else:
+            lp_gp = ctx.sparse_elbo(self.X, self.terms(ell), NOISE_VAR, fx, self.inducing, self.jitter)
         r = self.y - fx
         return -math.log(ELL_HI - ELL_LO) + lp_gp + float(np.sum(-(LOG2PI + r * r) / 2))
 

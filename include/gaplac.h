@@ -315,6 +315,30 @@ int gaplac_sparse_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, cons
                                      int64_t Mz, const double* Z, int64_t ldz, double jitter,
                                      int64_t Ms, const double* Xs, int64_t ldxs,
                                      double* out_mean, double* out_var);
+/* The bound and its gradient with respect to y, the term parameters, the observation variance
+ * and jitter (the inducing inputs Z stay fixed: a CAT column has no derivative). With c = S^{-1} w
+ * = L_S^{-T} u, alpha = (y - V^T c) / noise, ctil = L^{-T} c, Phi = I / noise - S^{-1},
+ * W' = L^{-T} Phi, G_uf = ctil alpha^T + W' V (Mz x N, never stored) and
+ * G_uu = -( ctil ctil^T + L^{-T} (S / noise - 2 I + noise S^{-1}) L^{-1} ) / 2:
+ *     out_dy[n]     = -alpha_n
+ *     out_dparam[t] = -sum_n dk(x_n, x_n)/dtheta_t / (2 noise) + sum G_uf o dK(Z, X)/dtheta_t
+ *                     + sum G_uu o dK(Z)/dtheta_t
+ *     out_dnoise    = ( alpha^T alpha - (N - Mz + noise tr S^{-1}) / noise ) / 2 + trace / (2 noise^2)
+ *     out_djitter   = tr G_uu
+ * dk/dtheta_t is gaplac_logpdf_grad's (l of SQEXP / OU, c of LINEAR, the variance of a NOISE term;
+ * 0 for CAT; times the other terms of t's product group); a NOISE term is 0 across point sets.
+ * out_elbo is bitwise gaplac_sparse_elbo's for the same arguments (the value runs by the same
+ * schedule first). The N-long work is one GEMV for alpha and one fp64-MFMA product with the
+ * contraction in its epilogue, reduced in a fixed order: a call is bitwise repeatable. out_dy has
+ * N entries, out_dparam T; every output except out_elbo may be NULL. Conventions, errors and the
+ * closed forms for N = 0 (everything 0) and Mz = 0 (dy = -y / noise, djitter = 0) as above.
+ * Replaces: the gradient of elbo(VFE(f(z, jitter)), f(x, noise), y) (no analytic form in the
+ * reference: AbstractGPs differentiates it by AD). */
+int gaplac_sparse_elbo_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                            int32_t T, const gaplac_term* terms, double noise, const double* y,
+                            int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                            double* out_elbo, double* out_dy, double* out_dparam, double* out_dnoise,
+                            double* out_djitter);
 /* Host-only: the split of the product for S over the N rows, *out_chunks chunks of
  * *out_chunk_rows rows (the last one ragged), summed in ascending order. A function of (N, Mz)
  * alone. GAPLAC_E_ARG for N < 0, Mz < 0 or a NULL output. Not in the reference. */
@@ -412,6 +436,13 @@ int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_
  * negative controls); 0: as allocated. Not in the reference. */
 int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws,
                              int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for gaplac_sparse_elbo_grad: gaplac_plan_check_sparse at Ms = 0, then the
+ * gradient's launches: the order-Mz ones against its scratch, alpha and the product kernel against
+ * the first workspace and the scratch. short_ws 1: the first workspace one element short; 2: the
+ * second workspace and the gradient's scratch one element short (the negative controls); 0: as
+ * allocated. Not in the reference. */
+int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws,
+                                  int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* Host-only accounting of the single-GPU schedule for order N (GAPLAC_SPW = spw,
  * GAPLAC_PAIR_DEPTH = depth (0: auto), band extension pair_ext (0/1), GAPLAC_PAIR_M =
  * pair_m): every tile column gets every earlier panel column exactly once, in order, before

@@ -12,6 +12,9 @@
 //   gaplac_plan_check_sparse   - the sparse entries' three stages (the posterior evaluation of
 //                                order Mz with N + Ms riding rows, the launches that form S, the
 //                                preloaded factorisation of order Mz) and gaplac_sparse_split;
+//   gaplac_plan_check_sparse_grad - the same for gaplac_sparse_elbo_grad: the value's stages,
+//                                the order-Mz launches against the gradient's scratch, alpha and
+//                                the product kernel against the first workspace and the scratch;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -114,6 +117,26 @@ int main() {
                        (long long)N, (long long)Ms);
             }
     EXPECT(gaplac_plan_check_sparse(10, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "sparse: Mz = 0 accepted");
+    // the gradient of the bound: the value's stages, the order-Mz launches against the scratch, alpha
+    // and the product kernel against the first workspace and the scratch; then each one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t Mz : {1, 5, 127, 128, 129, 257, 513, 1024, 4096})
+            for (int64_t N : {1, 5, 127, 128, 129, 300, 700, 1000, 2000, 2051, 16384, 262144}) {
+                const int rc = gaplac_plan_check_sparse_grad(N, Mz, spw, 0, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && a > 0 && b == 0, "plan_check_sparse_grad N=%lld Mz=%lld spw=%d: rc %d violations %lld %s",
+                       (long long)N, (long long)Mz, spw, rc, (long long)b, msg);
+                ++checks;
+            }
+    for (int short_ws : {1, 2})
+        for (int64_t N : {1, 128, 300, 4096})
+            for (int64_t Mz : {1, 129, 1000}) {
+                int64_t b0 = 0;
+                int rc = gaplac_plan_check_sparse(N, Mz, 0, 4, short_ws, &a, &b0, msg, sizeof msg);
+                rc = rc ? rc : gaplac_plan_check_sparse_grad(N, Mz, 4, short_ws, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && b >= b0 + 1, "negative control (sparse grad, short_ws %d) N=%lld Mz=%lld not reported",
+                       short_ws, (long long)N, (long long)Mz);
+            }
+    EXPECT(gaplac_plan_check_sparse_grad(10, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "sparse grad: Mz = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
