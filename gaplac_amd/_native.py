@@ -41,6 +41,7 @@ EXPORTED = (
     "gaplac_posterior_logpdf",
     "gaplac_sparse_elbo",
     "gaplac_sparse_elbo_grad",
+    "gaplac_sparse_elbo_grad_z",
     "gaplac_sparse_posterior_mean_var",
     "gaplac_sparse_split",
     "gaplac_gram",
@@ -54,6 +55,7 @@ EXPORTED = (
     "gaplac_plan_check_joint",
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
+    "gaplac_plan_check_sparse_grad_z",
     "gaplac_dist_create",
     "gaplac_dist_destroy",
     "gaplac_dist_last_error",
@@ -180,8 +182,11 @@ def load() -> ctypes.CDLL:
     sparse = common + [c_int64, c_void_p, c_int64, c_double]
     lib.gaplac_sparse_elbo.argtypes = sparse + [_DP, _DP, _DP, _DP, _DP]
     lib.gaplac_sparse_elbo_grad.argtypes = sparse + [_DP, c_void_p, c_void_p, _DP, _DP]
+    lib.gaplac_sparse_elbo_grad_z.argtypes = sparse + [_DP, c_void_p, c_void_p, _DP, _DP, c_void_p, c_int64]
     lib.gaplac_plan_check_sparse_grad.argtypes = [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
                                                   POINTER(c_int64), c_char_p, c_int64]
+    lib.gaplac_plan_check_sparse_grad_z.argtypes = [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int64),
+                                                    POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_sparse_posterior_mean_var.argtypes = sparse + [c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.gaplac_sparse_split.argtypes = [c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]
     lib.gaplac_plan_check_sparse.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),

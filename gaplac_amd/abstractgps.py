@@ -216,14 +216,16 @@ def elbo(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None, full: bo
     return (ctx or backend.default_context()).sparse_elbo(*args, full=full)
 
 
-def elbo_and_gradient(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):
+def elbo_and_gradient(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None, wrt_inducing: bool = False):
     """(elbo, dy, dparam, dnoise, djitter): the bound and its gradient with respect to y, the
     lowered terms' parameters, the observation variance and the jitter of f(z, jitter), the
-    inducing inputs fixed (gaplac_sparse_elbo_grad). AbstractGPs has no such method: a Julia host
-    differentiates elbo by AD."""
+    inducing inputs fixed (gaplac_sparse_elbo_grad). wrt_inducing=True appends dZ, the gradient
+    with respect to the inducing inputs (Mz x D, gaplac_sparse_elbo_grad_z). AbstractGPs has no
+    such method: a Julia host differentiates elbo by AD."""
     _gate()
     args = _vfe_args(vfe, fx, y)
-    return (ctx or backend.default_context()).sparse_elbo_grad(*args)
+    c = ctx or backend.default_context()
+    return c.sparse_elbo_grad(*args, wrt_z=True) if wrt_inducing else c.sparse_elbo_grad(*args)
 
 
 def dtc(vfe: VFE, fx: FiniteGP, y, ctx: backend.Context | None = None):

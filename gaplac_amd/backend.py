@@ -405,18 +405,27 @@ class Context:
         names = ("elbo", "dtc", "trace", "logdet", "quad")
         return {k: o.value for k, o in zip(names, out)} if full else out[0].value
 
-    def sparse_elbo_grad(self, X, terms, noise: float, y, Z, jitter: float = 0.0):
+    def sparse_elbo_grad(self, X, terms, noise: float, y, Z, jitter: float = 0.0, wrt_z: bool = False):
         """(elbo, dy, dparam, dnoise, djitter): the bound and its gradient with respect to y, the
-        term parameters, the observation variance and jitter (gaplac_sparse_elbo_grad)."""
-        head, keep, _ = self._sparse_head(X, terms, noise, y, Z, jitter)
+        term parameters, the observation variance and jitter (gaplac_sparse_elbo_grad). wrt_z=True
+        appends dZ, the gradient with respect to the inducing inputs, an (Mz, D) array
+        (gaplac_sparse_elbo_grad_z); the other five are bitwise the same either way."""
+        head, keep, D = self._sparse_head(X, terms, noise, y, Z, jitter)
         N, T = head[0], head[4]
         elbo, dnoise, djitter = c_double(), c_double(), c_double()
         dy = np.empty(N, dtype=np.float64)
         dparam = np.empty(T, dtype=np.float64)
         yb = dy if N else np.empty(1)  # (an empty result still passes valid pointers)
         pb = dparam if T else np.empty(1)
-        rc = self.lib.gaplac_sparse_elbo_grad(self.h, *head, byref(elbo), yb.ctypes.data_as(c_void_p),
-                                              pb.ctypes.data_as(c_void_p), byref(dnoise), byref(djitter))
+        outs = (byref(elbo), yb.ctypes.data_as(c_void_p), pb.ctypes.data_as(c_void_p), byref(dnoise), byref(djitter))
+        if wrt_z:
+            Mz = head[8]
+            dZ = np.empty((Mz, D), dtype=np.float64, order="F")
+            zb = dZ if dZ.size else np.empty(1)
+            rc = self.lib.gaplac_sparse_elbo_grad_z(self.h, *head, *outs, zb.ctypes.data_as(c_void_p), max(Mz, 1))
+            self._check(rc)
+            return elbo.value, dy, dparam, dnoise.value, djitter.value, dZ
+        rc = self.lib.gaplac_sparse_elbo_grad(self.h, *head, *outs)
         self._check(rc)
         return elbo.value, dy, dparam, dnoise.value, djitter.value
 

@@ -248,6 +248,9 @@ struct gaplac_ctx {
     size_t sg_dinv_elems = 0;
     double* sg_v = nullptr;
     size_t sg_v_elems = 0;
+    // The gradient with respect to the inducing inputs: partials and the result
+    double* sgz = nullptr;
+    size_t sgz_elems = 0;
     // gradient: alpha, partial sums, the XCD-balanced C^{-1} tile list
     double* galpha = nullptr;
     size_t galpha_elems = 0;
@@ -332,7 +335,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        buf(&c->mres), large(&c->dZ, &c->dZ_elems), large(&c->dO, &c->dO_elems),
                        large(&c->B, &c->B_elems), large(&c->sp_y, &c->sp_y_elems),
                        large(&c->sp_part, &c->sp_part_elems), large(&c->sg, &c->sg_elems),
-                       large(&c->sg_dinv, &c->sg_dinv_elems), large(&c->sg_v, &c->sg_v_elems)};
+                       large(&c->sg_dinv, &c->sg_dinv_elems), large(&c->sg_v, &c->sg_v_elems),
+                       large(&c->sgz, &c->sgz_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -1411,21 +1415,25 @@ int upload_test_inputs(gaplac_ctx* ctx, int32_t D, int64_t rows, int64_t r0, int
 // second region): a launch whose grid would leave them is not enqueued and the entry fails.
 template <typename Launches>
 int guarded_on(gaplac_ctx* ctx, const double* base, size_t elems, const double* base2, size_t elems2,
-               Launches&& launches);
+               Launches&& launches, const double* base3 = nullptr, size_t elems3 = 0);
 template <typename Launches>
 int guarded(gaplac_ctx* ctx, bool with_B, Launches&& launches) {
     return guarded_on(ctx, ctx->A, ctx->A_elems, with_B ? ctx->B : nullptr, with_B ? ctx->B_elems : 0, launches);
 }
-// The same over any two allocations (the second may be null).
+// The same over any two (or three) allocations (the second and third may be null).
 template <typename Launches>
 int guarded_on(gaplac_ctx* ctx, const double* base, size_t elems, const double* base2, size_t elems2,
-               Launches&& launches) {
+               Launches&& launches, const double* base3, size_t elems3) {
     LaunchGuard g;
     g.base = base;
     g.elems = (int64_t)elems;
     if (base2) {
         g.base2 = base2;
         g.elems2 = (int64_t)elems2;
+    }
+    if (base3) {
+        g.base3 = base3;
+        g.elems3 = (int64_t)elems3;
     }
     {
         GuardScope scope(&g);
@@ -2130,10 +2138,14 @@ void sparse_grad_alpha_launches(hipStream_t s, const SparseDims& d, const Sparse
 }
 void sparse_grad_uf_launches(hipStream_t s, const SparseDims& d, const SparseGradDims& g, int64_t N, int64_t Mz,
                              const double* A, const double* G, double* vec, double* part, const double* X,
-                             const double* Z, const TermPack* dtp, const GradTermPack* dgp, bool groups, int T) {
+                             const double* Z, const TermPack* dtp, const GradTermPack* dgp, bool groups, int T,
+                             double* dz = nullptr, int D = 0) {
     launch_sparse_guf(s, A, d.lda, d.Np, N, Mz, G + 2 * g.ld * g.Np + g.Np, g.ld, X, N, Z, Mz, vec + g.alpha,
-                      vec + g.ct, dtp, dgp, groups, part);
+                      vec + g.ct, dtp, dgp, groups, part, dz, T);
     launch_grad_reduce(s, part, (int)(((N + NB - 1) / NB) * ((Mz + NB - 1) / NB)), T, vec + g.out + SG_OUT_UF);
+    // dz (§10.10): the product above was its dZ variant; the reductions, the order-Mz part from G_uu
+    // (G3's upper slot) and the finishing step follow
+    if (dz) launch_sparse_dz(s, sparse_dz_dims(N, Mz, T, D), G + 2 * g.ld * g.Np, g.ld, Mz, T, D, Z, Mz, dtp, dgp, dz);
 }
 size_t sparse_grad_part_elems(int64_t N, int64_t Mz) {
     const size_t nk = (size_t)((Mz + 511) / 512), m = (size_t)((Mz + NB - 1) / NB), mt = (size_t)((N + NB - 1) / NB);
@@ -2163,12 +2175,15 @@ void host_dkdiag(const TermPack& tp, const GradTermPack& gp, const double* X, in
 int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                           const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
                           int64_t ldz, double jitter, double* out_elbo, double* out_dy, double* out_dparam,
-                          double* out_dnoise, double* out_djitter) {
+                          double* out_dnoise, double* out_djitter, double* out_dZ = nullptr, int64_t lddz = 0) {
     if (!ctx) return GAPLAC_E_ARG;
     for (double* o : {out_elbo, out_dnoise, out_djitter})
         if (o) *o = NAN;
     for (int t = 0; out_dparam && t < T && t < GAPLAC_MAX_TERMS; ++t) out_dparam[t] = NAN;
     for (int64_t n = 0; out_dy && n < N; ++n) out_dy[n] = NAN;
+    if (out_dZ && lddz < Mz) return set_err(ctx, GAPLAC_E_ARG, "lddz (%lld) < Mz (%lld)", (long long)lddz, (long long)Mz);
+    for (int32_t c = 0; out_dZ && c < D; ++c)
+        for (int64_t m = 0; m < Mz; ++m) out_dZ[(int64_t)c * lddz + m] = NAN;
     // the value, by its own schedule; with sg_keep its stages leave S and the first Dinv behind
     struct Keep {
         gaplac_ctx* c;
@@ -2204,6 +2219,9 @@ int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
         HIPCK(ctx, hipSetDevice(ctx->device));
         if ((rc = ensure(ctx, &ctx->sg_v, &ctx->sg_v_elems, (size_t)(g.alpha + N)))) return rc;
         if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, sparse_grad_part_elems(N, Mz)))) return rc;
+        const SparseDzDims zd = sparse_dz_dims(N, Mz, T, D);
+        if (out_dZ && (rc = ensure(ctx, &ctx->sgz, &ctx->sgz_elems, (size_t)zd.elems))) return rc;
+        double* const dz = out_dZ ? ctx->sgz : nullptr;
         // (the value has retired: ctx->A is the first workspace again, L above V^T; ctx->B holds L_S,
         // ctx->Dinv its inverses, ctx->dX = Z, ctx->dXs = X, ctx->dtp the pack)
         double* const G = ctx->sg;
@@ -2223,14 +2241,20 @@ int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
                  sparse_grad_alpha_launches(ctx->s_main, d, g, N, Mz, ctx->A, ctx->sg_v, ctx->gpart, noise, ctx->sp_y);
              })))
             return rc;
-        // <trace path>.sg: "N Mz ms" of the product kernel (and its reduction) alone
+        // <trace path>.sg: "N Mz ms" of the product kernel (and its reductions, dZ's included) alone
         rc = trace_timed(ctx, ".sg", N, Mz, [&] {
-            return guarded_on(ctx, ctx->A, ctx->A_elems, G, ctx->sg_elems, [&] {
-                sparse_grad_uf_launches(ctx->s_main, d, g, N, Mz, ctx->A, G, ctx->sg_v, ctx->gpart, ctx->dXs, ctx->dX,
-                                        ctx->dtp, ctx->dgp, groups, T);
-            });
+            return guarded_on(
+                ctx, ctx->A, ctx->A_elems, G, ctx->sg_elems,
+                [&] {
+                    sparse_grad_uf_launches(ctx->s_main, d, g, N, Mz, ctx->A, G, ctx->sg_v, ctx->gpart, ctx->dXs,
+                                            ctx->dX, ctx->dtp, ctx->dgp, groups, T, dz, D);
+                },
+                dz, dz ? ctx->sgz_elems : 0);
         });
         if (rc) return rc;
+        if (dz)
+            HIPCK(ctx, hipMemcpy2DAsync(out_dZ, (size_t)lddz * 8, dz + zd.out, (size_t)Mz * 8, (size_t)Mz * 8, (size_t)D,
+                                        hipMemcpyDeviceToHost, ctx->s_main));
         HIPCK(ctx, hipMemcpyAsync(alpha.data(), ctx->sg_v + g.alpha, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->s_main));
         HIPCK(ctx, hipMemcpyAsync(outs, ctx->sg_v + g.out, sizeof outs, hipMemcpyDeviceToHost, ctx->s_main));
         HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
@@ -2245,6 +2269,9 @@ int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
     if (out_dnoise)
         *out_dnoise = N > 0 ? 0.5 * (ata - ((double)N / noise - outs[SG_OUT_TR])) + trace / (2.0 * noise * noise) : 0.0;
     if (out_djitter) *out_djitter = N > 0 ? 2.0 * outs[SG_OUT_UU + T] : 0.0;
+    if (N == 0)  // no data: the bound is 0 whatever Z is
+        for (int32_t c = 0; out_dZ && c < D; ++c)
+            for (int64_t m = 0; m < Mz; ++m) out_dZ[(int64_t)c * lddz + m] = 0.0;
     return 0;
 }
 
@@ -2965,6 +2992,14 @@ int gaplac_sparse_elbo_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double*
                                  out_dparam, out_dnoise, out_djitter);
 }
 
+int gaplac_sparse_elbo_grad_z(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                              const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                              int64_t ldz, double jitter, double* out_elbo, double* out_dy, double* out_dparam,
+                              double* out_dnoise, double* out_djitter, double* out_dZ, int64_t lddz) {
+    return sparse_elbo_grad_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, out_elbo, out_dy,
+                                 out_dparam, out_dnoise, out_djitter, out_dZ, lddz);
+}
+
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {
     if (N < 0 || Mz < 0 || !out_chunks || !out_chunk_rows) return GAPLAC_E_ARG;
     sparse_split(N, Mz, out_chunks, out_chunk_rows);
@@ -3026,10 +3061,13 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
 // scratch as its second region. short_ws 1: the first workspace one element short (the value's
 // walk and the product kernel's riding rows both leave it); 2: the second workspace of the value
 // and the gradient's scratch one element short (negative controls).
-int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws, int64_t* out_launches,
-                                  int64_t* out_violations, char* msg, int64_t msglen) {
+// With Tz > 0 it is gaplac_sparse_elbo_grad_z's walk (§10.10): the product kernel's dZ variant in
+// the product's place and the dZ launches after it, the buffer of dZ's partials as the third
+// region, one element short with short_ws 3.
+static int plan_sparse_grad(int64_t N, int64_t Mz, int32_t Tz, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                            int64_t* out_violations, char* msg, int64_t msglen) {
     int64_t l0 = 0, v0 = 0;
-    int rc = gaplac_plan_check_sparse(N, Mz, 0, spw, short_ws, &l0, &v0, msg, msglen);
+    int rc = gaplac_plan_check_sparse(N, Mz, 0, spw, short_ws == 3 ? 0 : short_ws, &l0, &v0, msg, msglen);
     if (rc) return rc;
     const SparseDims d = sparse_dims(N, Mz, 0);
     const SparseGradDims g = sparse_grad_dims(Mz);
@@ -3045,6 +3083,11 @@ int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t sh
     g2.base2 = fg;
     g2.elems2 = g1.elems;
     g2.dry = true;
+    double* const fz = Tz > 0 ? reinterpret_cast<double*>((uintptr_t)1 << 47) : nullptr;
+    if (fz) {  // (one column of Z: the finishing step's store is the buffer's last element for any D)
+        g2.base3 = fz;
+        g2.elems3 = sparse_dz_dims(N, Mz, Tz, 1).elems - (short_ws == 3 ? 1 : 0);
+    }
     {
         GuardScope scope(&g1);
         sparse_grad_mz_launches(nullptr, g, Mz, fg, fv, fv, fv, fv, 1.0, nullptr, nullptr, nullptr, 1);
@@ -3052,13 +3095,26 @@ int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t sh
     {
         GuardScope scope(&g2);
         sparse_grad_alpha_launches(nullptr, d, g, N, Mz, fa, fv, fv, 1.0, nullptr);
-        sparse_grad_uf_launches(nullptr, d, g, N, Mz, fa, fg, fv, fv, nullptr, nullptr, nullptr, nullptr, false, 1);
+        sparse_grad_uf_launches(nullptr, d, g, N, Mz, fa, fg, fv, fv, nullptr, nullptr, nullptr, nullptr, false,
+                                fz ? Tz : 1, fz, 1);
     }
     if (out_launches) *out_launches = l0 + g1.launches + g2.launches;
     if (out_violations) *out_violations = v0 + g1.violations + g2.violations;
     if (msg && msglen > 0 && v0 == 0 && (g1.violations || g2.violations))
         std::snprintf(msg, (size_t)msglen, "%s", (g1.violations ? g1.first : g2.first).c_str());
     return 0;
+}
+
+int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                                  int64_t* out_violations, char* msg, int64_t msglen) {
+    if (short_ws == 3) return GAPLAC_E_ARG;
+    return plan_sparse_grad(N, Mz, 0, spw, short_ws, out_launches, out_violations, msg, msglen);
+}
+
+int gaplac_plan_check_sparse_grad_z(int64_t N, int64_t Mz, int32_t T, int32_t spw, int32_t short_ws,
+                                    int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) {
+    if (T < 1 || T > GAPLAC_MAX_TERMS || short_ws < 0 || short_ws > 3) return GAPLAC_E_ARG;
+    return plan_sparse_grad(N, Mz, T, spw, short_ws, out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior

@@ -208,6 +208,9 @@ struct LaunchGuard {
     // posterior's covariance kernel writes while it reads the first
     const double* base2 = nullptr;
     int64_t elems2 = 0;
+    // a third (region 2): the partials of the gradient with respect to the inducing inputs (§10.10)
+    const double* base3 = nullptr;
+    int64_t elems3 = 0;
     bool dry = false;
     int64_t launches = 0;
     int64_t violations = 0;
@@ -390,7 +393,22 @@ void launch_sparse_alpha(hipStream_t s, const double* A, int64_t lda, int64_t Np
 // coordinates (ld ldx), Z: the columns'. groups: the formula has product groups (the slower kernel).
 void launch_sparse_guf(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t Mz, const double* W,
                        int64_t ldw, const double* X, int64_t ldx, const double* Z, int64_t ldz, const double* alpha,
-                       const double* ctil, const TermPack* dtp, const GradTermPack* dgp, bool groups, double* partial);
+                       const double* ctil, const TermPack* dtp, const GradTermPack* dgp, bool groups, double* partial,
+                       double* dz = nullptr, int T = 0);
+// The gradient with respect to the inducing inputs. One buffer dz (the guard's
+// third allocation) holds, in this order: part, one partial per (row tile of X, term, m), which the
+// dZ variant of the product kernel writes when launch_sparse_guf is given dz and T; rows, their sum
+// over the row tiles; uu, the order-Mz part per (column tile of G_uu, term, m); out, dZ (Mz x D,
+// leading dimension Mz). ld = 128 ceil(Mz / 128) is the stride between terms.
+struct SparseDzDims {
+    int64_t mt, ntm, ld, part, rows, uu, out, elems;
+};
+SparseDzDims sparse_dz_dims(int64_t N, int64_t Mz, int T, int D);
+// After launch_sparse_guf with dz: the row tiles summed in ascending order, the order-Mz part from
+// G_uu (the full Mz x Mz square at Guu, leading dimension ldg, in the guard's second allocation),
+// and the finishing step that folds the terms into their columns of Z, in term order.
+void launch_sparse_dz(hipStream_t s, const SparseDzDims& z, const double* Guu, int64_t ldg, int64_t Mz, int T, int D,
+                      const double* Z, int64_t ldz, const TermPack* dtp, const GradTermPack* dgp, double* dz);
 // O[:, c] += mean, c < R (O is M x R, leading dimension ldo).
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean);
 // After the factorisation and launch_reduce (same stream): quad_r = sum_k W^T[r,k]^2 and

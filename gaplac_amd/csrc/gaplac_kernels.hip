@@ -2056,6 +2056,73 @@ __device__ __forceinline__ double dk_ou(double p, double xi, double xj, const do
     const double a = fabs(p * xi - p * xj);
     return exp_nonpos(-a, tbl) * a * p;
 }
+// The same two values (the same operations in the same order, so bitwise the same), and in d2
+// the derivative in the coordinate xj: d/dxj exp(-u^2/2) = k u / l, d/dxj exp(-|u|) = k sign(u) / l
+// with u = (xi - xj) / l; sign(0) = 0, the symmetric subgradient at OU's kink.
+__device__ __forceinline__ double dk_sqexp_d2(double p, double xi, double xj, const double* tbl, double& d2) {
+#pragma clang fp contract(off)
+    const double u = p * xi - p * xj;
+    const double u2 = u * u;
+    const double e = exp_nonpos(-u2 * 0.5, tbl);
+    d2 = e * u * p;
+    return e * u2 * p;
+}
+__device__ __forceinline__ double dk_ou_d2(double p, double xi, double xj, const double* tbl, double& d2) {
+#pragma clang fp contract(off)
+    const double u = p * xi - p * xj;
+    const double a = fabs(u);
+    const double e = exp_nonpos(-a, tbl);
+    const double ep = e * p;
+    d2 = u > 0.0 ? ep : (u < 0.0 ? -ep : 0.0);
+    return e * a * p;
+}
+// term_dk(kind, p, xi, xj, false) (the same operations: bitwise the same) and term_d2 in d2, one exp
+__device__ __forceinline__ double term_dk_d2(int kind, double p, double xi, double xj, double& d2) {
+#pragma clang fp contract(off)
+    d2 = 0.0;
+    switch (kind) {
+        case GAPLAC_SQEXP: {
+            const double u = p * xi - p * xj;
+            const double u2 = u * u;
+            const double e = exp(-u2 * 0.5);
+            d2 = e * u * p;
+            return e * u2 * p;
+        }
+        case GAPLAC_OU: {
+            const double u = p * xi - p * xj;
+            const double a = fabs(u);
+            const double e = exp(-a);
+            const double ep = e * p;
+            d2 = u > 0.0 ? ep : (u < 0.0 ? -ep : 0.0);
+            return e * a * p;
+        }
+        case GAPLAC_LINEAR:
+            d2 = xi;
+            return 1.0;
+        default:  // CAT; a NOISE term is 0 across point sets
+            return 0.0;
+    }
+}
+// dk(xi, xj)/dxj of any term kind, term_k's arithmetic (libm exp): the product-group path and
+// the order-Mz kernel. LINEAR: d/dxj (xi xj + c) = xi; CAT and NOISE: 0.
+__device__ __forceinline__ double term_d2(int kind, double p, double xi, double xj) {
+#pragma clang fp contract(off)
+    switch (kind) {
+        case GAPLAC_SQEXP: {
+            const double u = p * xi - p * xj;
+            return exp(-(u * u) * 0.5) * u * p;
+        }
+        case GAPLAC_OU: {
+            const double u = p * xi - p * xj;
+            const double ep = exp(-fabs(u)) * p;
+            return u > 0.0 ? ep : (u < 0.0 ? -ep : 0.0);
+        }
+        case GAPLAC_LINEAR:
+            return xi;
+        default:
+            return 0.0;
+    }
+}
 
 // -C^{-1} tile (I, J) as cinv_tile_kernel computes it, contracted in place with every
 // dC/dtheta (grad_contract_kernel's sum over the tile) instead of being stored: the tile
@@ -3069,14 +3136,18 @@ __global__ __launch_bounds__(256) void sparse_alpha_finish_kernel(const double* 
 // 1) + t], t < T; slot T is 0. GROUPS: terms inside product groups carry the group's other
 // terms (term_k's arithmetic, a second set of 64 weights: the slower path); without it such a
 // term's slot is not meaningful and the host never launches that variant for such a formula.
-template <bool GROUPS>
+// DZ: also the per-column sums for the gradient in the inducing inputs (sparse_guf_dz_kernel
+// below); without it every DZ branch is dead and the two kernels of §10.9
+// compile as they did.
+template <bool GROUPS, bool DZ>
 __device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, int64_t lda, int64_t Np,
                                                 const double* __restrict__ W, int64_t ldw, int64_t N, int64_t Mz,
                                                 const double* __restrict__ X, int64_t ldx,
                                                 const double* __restrict__ Z, int64_t ldz,
                                                 const double* __restrict__ alpha, const double* __restrict__ ctil,
                                                 const TermPack* __restrict__ tpp,
-                                                const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
+                                                const GradTermPack* __restrict__ gpp, double* __restrict__ partial,
+                                                double* __restrict__ dzpart, int64_t dzld) {
     __shared__ MmaLds sm;
     const int bm = (int)blockIdx.x, bn = (int)blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -3101,6 +3172,7 @@ __device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, in
 #else
     __shared__ double red[4 * (GAPLAC_MAX_TERMS + 1)];
 #endif
+    double* const dzl = tbl + 256 + 4 * (GAPLAC_MAX_TERMS + 1);  // DZ: dzl[(2 t + wi) * 128 + c]
     const int64_t r0 = (int64_t)bn * NB, c0 = (int64_t)bm * NB;
     for (int idx = tid; idx < T * NB; idx += 256) {
         const int t = idx / NB, q = idx % NB;
@@ -3132,9 +3204,53 @@ __device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, in
 #pragma unroll 1
     for (int t = 0; t <= T; ++t) {
         double g = 0.0;
+        d4 cs[4];  // DZ: the lane's 16 columns (mj, rg), summed over its 4 row groups mi
+        if (DZ) {
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj) cs[mj] = d4{0.0, 0.0, 0.0, 0.0};
+        }
         const int kind = t < T ? tp.kind[t] : GAPLAC_CAT;  // (slot T: nothing)
         const int gs = t < T ? gpp->gstart[t] : 0, ge = t < T ? gpp->gend[t] : 1;
-        if (GROUPS && ge - gs > 1) {
+        if (GROUPS && DZ && ge - gs > 1) {
+            // One row group at a time, in a run-time loop whose body exists once: 16 group weights
+            // live instead of 64 (the 16 column sums take their registers), and nothing of one row
+            // group is scheduled into the next. Every weight is the same product in the same order
+            // and g the same sum in the same order as below, so partial stays bitwise
+            // sparse_guf_groups_kernel's.
+            const double p = tp.p[t];
+#pragma unroll 1
+            for (int mi = 0; mi < 4; ++mi) {
+                d4 wr[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (q == mi) {
+#pragma unroll
+                        for (int mj = 0; mj < 4; ++mj) wr[mj] = acc[q][mj];
+                    }
+#pragma unroll 1
+                for (int s2 = gs; s2 < ge; ++s2) {
+                    if (s2 == t) continue;
+                    const int k2 = tp.kind[s2];
+                    const double p2 = tp.p[s2];
+                    const double xi = xr[s2 * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                    for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                        for (int rg = 0; rg < 4; ++rg)
+                            wr[mj][rg] *= term_k(k2, p2, xi, xc[s2 * NB + 64 * wj + 16 * mj + fr + 4 * rg], false);
+                }
+                const double xi = xr[t * NB + 64 * wi + 16 * mi + fc];
+#pragma unroll
+                for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                    for (int rg = 0; rg < 4; ++rg) {
+                        const double xj = xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg];
+                        double d2;
+                        g += wr[mj][rg] * term_dk_d2(kind, p, xi, xj, d2);
+                        cs[mj][rg] += wr[mj][rg] * d2;
+                    }
+            }
+        } else if (GROUPS && ge - gs > 1) {
             const double p = tp.p[t];
             d4 wm[4][4];
 #pragma unroll
@@ -3173,8 +3289,15 @@ __device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, in
 #pragma unroll
                 for (int mj = 0; mj < 4; ++mj)
 #pragma unroll
-                    for (int rg = 0; rg < 4; ++rg)
-                        g += acc[mi][mj][rg] * dk_sqexp(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+                    for (int rg = 0; rg < 4; ++rg) {
+                        if (DZ) {
+                            double d2;
+                            g += acc[mi][mj][rg] * dk_sqexp_d2(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl, d2);
+                            cs[mj][rg] += acc[mi][mj][rg] * d2;
+                        } else {
+                            g += acc[mi][mj][rg] * dk_sqexp(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+                        }
+                    }
             }
         } else if (kind == GAPLAC_OU) {
             const double p = tp.p[t];
@@ -3184,25 +3307,54 @@ __device__ __forceinline__ void sparse_guf_body(const double* __restrict__ A, in
 #pragma unroll
                 for (int mj = 0; mj < 4; ++mj)
 #pragma unroll
-                    for (int rg = 0; rg < 4; ++rg)
-                        g += acc[mi][mj][rg] * dk_ou(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+                    for (int rg = 0; rg < 4; ++rg) {
+                        if (DZ) {
+                            double d2;
+                            g += acc[mi][mj][rg] * dk_ou_d2(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl, d2);
+                            cs[mj][rg] += acc[mi][mj][rg] * d2;
+                        } else {
+                            g += acc[mi][mj][rg] * dk_ou(p, xi, xc[t * NB + 64 * wj + 16 * mj + fr + 4 * rg], tbl);
+                        }
+                    }
             }
         } else if (kind == GAPLAC_LINEAR) {  // d/dc (x z + c) = 1
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
+            for (int mi = 0; mi < 4; ++mi) {
+                const double xi = DZ ? xr[t * NB + 64 * wi + 16 * mi + fc] : 0.0;  // d/dz (x z + c) = x
 #pragma unroll
                 for (int mj = 0; mj < 4; ++mj)
 #pragma unroll
-                    for (int rg = 0; rg < 4; ++rg) g += acc[mi][mj][rg];
+                    for (int rg = 0; rg < 4; ++rg) {
+                        g += acc[mi][mj][rg];
+                        if (DZ) cs[mj][rg] += acc[mi][mj][rg] * xi;
+                    }
+            }
         }  // Cat: no parameter; Noise: 0 across point sets
         const double x = wave_sum(g);
         if (lane == 0) red[w * (T + 1) + t] = x;
+        if (DZ && t < T) {  // a column's 64 rows of this wave: the 16 lanes that share fr
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg) {
+                    double c = cs[mj][rg];
+#pragma unroll
+                    for (int o = 1; o < 16; o <<= 1) c += __shfl_xor(c, o, 64);
+                    if (fc == 0) dzl[(2 * t + wi) * NB + 64 * wj + 16 * mj + fr + 4 * rg] = c;
+                }
+        }
     }
     __syncthreads();
     if (tid <= T) {
         const int64_t b = (int64_t)bn * gridDim.x + bm;
         const int S = T + 1;
         partial[b * S + tid] = (red[tid] + red[S + tid]) + (red[2 * S + tid] + red[3 * S + tid]);
+    }
+    if (DZ) {  // the two row halves in order: one partial per (row tile, term, column)
+        for (int idx = tid; idx < T * NB; idx += 256) {
+            const int t = idx / NB, c = idx % NB;
+            dzpart[((int64_t)bn * T + t) * dzld + c0 + c] = dzl[(2 * t) * NB + c] + dzl[(2 * t + 1) * NB + c];
+        }
     }
 }
 
@@ -3211,7 +3363,7 @@ __global__ __launch_bounds__(256, 2) void sparse_guf_kernel(
     int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
     const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
     const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
-    sparse_guf_body<false>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial);
+    sparse_guf_body<false, false>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial, nullptr, 0);
 }
 // (one workgroup per CU: the second set of weights takes the registers of a second workgroup)
 __global__ __launch_bounds__(256) void sparse_guf_groups_kernel(
@@ -3219,7 +3371,113 @@ __global__ __launch_bounds__(256) void sparse_guf_groups_kernel(
     int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
     const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
     const GradTermPack* __restrict__ gpp, double* __restrict__ partial) {
-    sparse_guf_body<true>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial);
+    sparse_guf_body<true, false>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial, nullptr, 0);
+}
+
+// ---- the gradient with respect to the inducing inputs ----
+// The dZ variants of the two product kernels: the same k-loop and the same scalar epilogue in the
+// same order (partial is bitwise theirs), and for every term t the weights times dk_t(z_m, x_n)/dz_m
+// (times the group's other terms) summed over the tile's rows n for each of its 128 columns m:
+// over mi in the lane, a 16-lane butterfly over fc, then the two row halves wi = 0, 1 in order
+// through the staging LDS. dzpart[(blockIdx.y T + t) dzld + m], dzld = 128 gridDim.x; terms that
+// share a column of Z are folded later, in term order (sparse_dz_finish_kernel). No atomics.
+static_assert(sizeof(MmaLds) >= (4 * GAPLAC_MAX_TERMS * NB + 2 * NB + 256 + 4 * (GAPLAC_MAX_TERMS + 1)) * sizeof(double),
+              "the dZ variant's per-column sums must fit the staging LDS");
+__global__ __launch_bounds__(256, 2) void sparse_guf_dz_kernel(
+    const double* __restrict__ A, int64_t lda, int64_t Np, const double* __restrict__ W, int64_t ldw, int64_t N,
+    int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
+    const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
+    const GradTermPack* __restrict__ gpp, double* __restrict__ partial, double* __restrict__ dzpart, int64_t dzld) {
+    sparse_guf_body<false, true>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial, dzpart,
+                                 dzld);
+}
+__global__ __launch_bounds__(256) void sparse_guf_dz_groups_kernel(
+    const double* __restrict__ A, int64_t lda, int64_t Np, const double* __restrict__ W, int64_t ldw, int64_t N,
+    int64_t Mz, const double* __restrict__ X, int64_t ldx, const double* __restrict__ Z, int64_t ldz,
+    const double* __restrict__ alpha, const double* __restrict__ ctil, const TermPack* __restrict__ tpp,
+    const GradTermPack* __restrict__ gpp, double* __restrict__ partial, double* __restrict__ dzpart, int64_t dzld) {
+    sparse_guf_body<true, true>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, tpp, gpp, partial, dzpart,
+                                dzld);
+}
+
+// out[i] = sum over the mt row tiles b, ascending, of dzpart[b TM + i], i < TM = T dzld.
+__global__ __launch_bounds__(64) void sparse_dz_rows_kernel(const double* __restrict__ dzpart, int64_t mt, int64_t TM,
+                                                            double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= TM) return;
+    double s = 0.0;
+    int64_t b = 0;
+    for (; b + 8 <= mt; b += 8) {  // eight loads in flight, added in order (one chain: the sum is the plain loop's)
+        double v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[q] = dzpart[(b + q) * TM + i];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += v[q];
+    }
+    for (; b < mt; ++b) s += dzpart[b * TM + i];
+    out[i] = s;
+}
+
+// The order-Mz part: block (x, y) = rows m of tile x against the columns m' of tile y of G_uu
+// (G[m' ld + m], the full square), uupart[(y T + t) dzld + m] = sum over the tile's m' < Mz,
+// ascending, of G_uu[m, m'] dk_t(z_m, z_m')/dz_m times the other terms of t's group (the m' = m
+// entry included: LINEAR's z_m, a NOISE factor's delta). The factor 2 enters in the finish.
+__global__ __launch_bounds__(128) void sparse_dz_uu_kernel(const double* __restrict__ G, int64_t ld, int64_t Mz,
+                                                           const double* __restrict__ Z, int64_t ldz,
+                                                           const TermPack* __restrict__ tpp,
+                                                           const GradTermPack* __restrict__ gpp,
+                                                           double* __restrict__ uupart, int64_t dzld) {
+    __shared__ double zr[GAPLAC_MAX_TERMS * NB], zc[GAPLAC_MAX_TERMS * NB];
+    const TermPack& tp = *tpp;
+    const int T = tp.T, tid = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * NB, c0 = (int64_t)blockIdx.y * NB;
+    for (int idx = tid; idx < T * NB; idx += NB) {
+        const int t = idx / NB, q = idx % NB;
+        const bool x = tp.kind[t] != GAPLAC_NOISE;
+        zr[idx] = (x && r0 + q < Mz) ? Z[(int64_t)tp.col[t] * ldz + r0 + q] : 0.0;
+        zc[idx] = (x && c0 + q < Mz) ? Z[(int64_t)tp.col[t] * ldz + c0 + q] : 0.0;
+    }
+    __syncthreads();
+    const int64_t i = r0 + tid;
+    const int nc = (int)((Mz - c0) < NB ? (Mz - c0) : NB);
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        const int kind = tp.kind[t], gs = gpp->gstart[t], ge = gpp->gend[t];
+        const double p = tp.p[t], zi = zr[t * NB + tid];
+        double s = 0.0;
+        if (i < Mz && (kind == GAPLAC_SQEXP || kind == GAPLAC_OU || kind == GAPLAC_LINEAR)) {
+            for (int cc = 0; cc < nc; ++cc) {
+                double d = term_d2(kind, p, zc[t * NB + cc], zi);
+                for (int s2 = gs; s2 < ge; ++s2)
+                    if (s2 != t) d *= term_k(tp.kind[s2], tp.p[s2], zr[s2 * NB + tid], zc[s2 * NB + cc], i == c0 + cc);
+                s += G[(c0 + cc) * ld + i] * d;
+            }
+        }
+        uupart[((int64_t)blockIdx.y * T + t) * dzld + i] = s;
+    }
+}
+
+// dZ[d Mz + m] = sum over the terms t that read column d (SQEXP, OU, LINEAR), in term order, of
+// the N-long part plus twice the order-Mz part, its column tiles summed in ascending order;
+// exactly +0.0 where no such term reads the column. blockIdx.y is the column d.
+__global__ __launch_bounds__(128) void sparse_dz_finish_kernel(const double* __restrict__ rows,
+                                                               const double* __restrict__ uupart, int ntm, int64_t dzld,
+                                                               int64_t Mz, const TermPack* __restrict__ tpp,
+                                                               double* __restrict__ dZ) {
+    const int64_t m = (int64_t)blockIdx.x * 128 + threadIdx.x;
+    const int d = (int)blockIdx.y;
+    if (m >= Mz) return;
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t) {
+        const int kind = tp.kind[t];
+        if (tp.col[t] != d || !(kind == GAPLAC_SQEXP || kind == GAPLAC_OU || kind == GAPLAC_LINEAR)) continue;
+        double uu = 0.0;
+        for (int b = 0; b < ntm; ++b) uu += uupart[((int64_t)b * T + t) * dzld + m];
+        acc += rows[(int64_t)t * dzld + m] + 2.0 * uu;
+    }
+    dZ[(int64_t)d * Mz + m] = acc;
 }
 
 // =================================================================================
@@ -4180,8 +4438,8 @@ bool guard_launch(const char* what, const double* p, int64_t lo, int64_t hi, int
     LaunchGuard* g = current_guard();
     if (!g) return true;
     ++g->launches;
-    const double* base = region ? g->base2 : g->base;
-    const int64_t elems = region ? g->elems2 : g->elems;
+    const double* base = region == 2 ? g->base3 : region ? g->base2 : g->base;
+    const int64_t elems = region == 2 ? g->elems3 : region ? g->elems2 : g->elems;
     if (base) {
         const int64_t off = (int64_t)(((intptr_t)p - (intptr_t)base) / (intptr_t)sizeof(double));
         if (lo > hi || off + lo < 0 || off + hi > elems) {
@@ -4628,20 +4886,60 @@ void launch_sparse_alpha(hipStream_t s, const double* A, int64_t lda, int64_t Np
 void launch_sparse_guf(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t Mz, const double* W,
                        int64_t ldw, const double* X, int64_t ldx, const double* Z, int64_t ldz, const double* alpha,
                        const double* ctil, const TermPack* dtp, const GradTermPack* dgp, bool groups,
-                       double* partial) {
+                       double* partial, double* dz, int T) {
     if (Mz <= 0 || N <= 0) return;
     const int64_t mt = (N + NB - 1) / NB, ntm = (Mz + NB - 1) / NB;
     // reads the mt tile rows of riding rows of every column of A, and rows < ntm 128 of every column of W
     const bool a_ok = guard_launch("sparse_guf_kernel (riding rows)", A, Np, (Np - 1) * lda + Np + mt * NB);
     const bool w_ok = guard_launch("sparse_guf_kernel (W')", W, 0, (Np - 1) * ldw + ntm * NB, 1);
-    if (!a_ok || !w_ok) return;
+    // the dZ variant also writes one partial per (row tile, term, column of the ntm tiles)
+    const bool z_ok = !dz || guard_launch("sparse_guf_dz_kernel (partials)", dz, 0, mt * T * ntm * NB, 2);
+    if (!a_ok || !w_ok || !z_ok) return;
     const dim3 grid((unsigned)ntm, (unsigned)mt);
-    if (groups)
+    if (dz && groups)
+        sparse_guf_dz_groups_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil,
+                                                               dtp, dgp, partial, dz, ntm * NB);
+    else if (dz)
+        sparse_guf_dz_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, dtp, dgp,
+                                                        partial, dz, ntm * NB);
+    else if (groups)
         sparse_guf_groups_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, dtp,
                                                             dgp, partial);
     else
         sparse_guf_kernel<<<grid, dim3(256), 0, s>>>(A, lda, Np, W, ldw, N, Mz, X, ldx, Z, ldz, alpha, ctil, dtp, dgp,
                                                      partial);
+}
+
+SparseDzDims sparse_dz_dims(int64_t N, int64_t Mz, int T, int D) {
+    SparseDzDims z;
+    z.mt = (N + NB - 1) / NB;
+    z.ntm = (Mz + NB - 1) / NB;
+    z.ld = z.ntm * NB;
+    z.part = 0;
+    z.rows = z.mt * T * z.ld;
+    z.uu = z.rows + T * z.ld;
+    z.out = z.uu + z.ntm * T * z.ld;
+    z.elems = z.out + Mz * D;
+    return z;
+}
+
+void launch_sparse_dz(hipStream_t s, const SparseDzDims& z, const double* Guu, int64_t ldg, int64_t Mz, int T, int D,
+                      const double* Z, int64_t ldz, const TermPack* dtp, const GradTermPack* dgp, double* dz) {
+    if (Mz <= 0 || z.mt <= 0 || T <= 0 || D <= 0) return;
+    const int64_t TM = T * z.ld;
+    const bool p_ok = guard_launch("sparse_dz_rows_kernel (partials)", dz + z.part, 0, z.mt * TM, 2);
+    const bool r_ok = guard_launch("sparse_dz_rows_kernel", dz + z.rows, 0, TM, 2);
+    if (p_ok && r_ok)
+        sparse_dz_rows_kernel<<<dim3((unsigned)((TM + 63) / 64)), dim3(64), 0, s>>>(dz + z.part, z.mt, TM, dz + z.rows);
+    // reads rows and columns < Mz of G_uu, writes one value per (column tile, term, row of the ntm tiles)
+    const bool g_ok = guard_launch("sparse_dz_uu_kernel (G_uu)", Guu, 0, (Mz - 1) * ldg + Mz, 1);
+    const bool u_ok = guard_launch("sparse_dz_uu_kernel", dz + z.uu, 0, z.ntm * TM, 2);
+    if (g_ok && u_ok)
+        sparse_dz_uu_kernel<<<dim3((unsigned)z.ntm, (unsigned)z.ntm), dim3(128), 0, s>>>(Guu, ldg, Mz, Z, ldz, dtp, dgp,
+                                                                                      dz + z.uu, z.ld);
+    if (guard_launch("sparse_dz_finish_kernel", dz + z.out, 0, Mz * D, 2) && p_ok && r_ok && g_ok && u_ok)
+        sparse_dz_finish_kernel<<<dim3((unsigned)z.ntm, (unsigned)D), dim3(128), 0, s>>>(
+            dz + z.rows, dz + z.uu, (int)z.ntm, z.ld, Mz, dtp, dz + z.out);
 }
 
 void launch_add_mean(hipStream_t s, double* O, int64_t ldo, int64_t M, int64_t R, const double* mean) {

@@ -339,6 +339,31 @@ int gaplac_sparse_elbo_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double*
                             int64_t Mz, const double* Z, int64_t ldz, double jitter,
                             double* out_elbo, double* out_dy, double* out_dparam, double* out_dnoise,
                             double* out_djitter);
+/* gaplac_sparse_elbo_grad, and the gradient with respect to the inducing inputs. For inducing
+ * point m and column d of Z, with G_uf and G_uu as above:
+ *     out_dZ[d lddz + m] = sum over the terms t with col_t = d of
+ *           sum_n  G_uf[m, n]  d1 k_t(z_m, x_n)  prod_{s != t in t's group} k_s(z_m, x_n)
+ *       + 2 sum_m' G_uu[m, m'] d1 k_t(z_m, z_m') prod_{s != t in t's group} k_s(z_m, z_m')
+ * d1 k(a, b) is the derivative in the first argument's coordinate: -k (a - b) / l^2 for SQEXP,
+ * -k sign(a - b) / l for OU, b for LINEAR, 0 for CAT and NOISE. For OU sign(0) = 0: at coinciding
+ * coordinates the kernel has a kink and the entry returns the symmetric subgradient. The m' = m
+ * term is kept (2 G_uu[m, m] z_m for LINEAR); a NOISE factor inside a product group is the delta
+ * of m and m' in K(Z) and 0 across point sets, as in the value. out_dZ is Mz x D column-major with
+ * leading dimension lddz >= Mz; rows Mz .. lddz - 1 are never written; a column that no SQEXP / OU /
+ * LINEAR term reads is exactly +0.0. With out_dZ == NULL the call is gaplac_sparse_elbo_grad
+ * (nothing more is launched or allocated). Every other output is bitwise gaplac_sparse_elbo_grad's
+ * for the same arguments, whether or not out_dZ is NULL. The sums over the rows n run in the
+ * product kernel's epilogue, per 128 rows, and those partials and the column tiles of G_uu are
+ * added in ascending order, the terms that share a column in term order: a call is bitwise
+ * repeatable. Conventions and errors as gaplac_sparse_elbo_grad; GAPLAC_E_ARG also for lddz < Mz
+ * with a non-NULL out_dZ (out_dZ is then left as it was; the other outputs are NaN). N = 0: dZ is
+ * all 0; Mz = 0: nothing is written; after a PosDefException every entry is NaN.
+ * Replaces: the gradient of the same bound with respect to z (AD in the reference's stack). */
+int gaplac_sparse_elbo_grad_z(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                              int32_t T, const gaplac_term* terms, double noise, const double* y,
+                              int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                              double* out_elbo, double* out_dy, double* out_dparam, double* out_dnoise,
+                              double* out_djitter, double* out_dZ, int64_t lddz);
 /* Host-only: the split of the product for S over the N rows, *out_chunks chunks of
  * *out_chunk_rows rows (the last one ragged), summed in ascending order. A function of (N, Mz)
  * alone. GAPLAC_E_ARG for N < 0, Mz < 0 or a NULL output. Not in the reference. */
@@ -443,6 +468,14 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
  * allocated. Not in the reference. */
 int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws,
                                   int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for gaplac_sparse_elbo_grad_z with T terms and a non-NULL out_dZ: the walk of
+ * gaplac_plan_check_sparse_grad with the product kernel's dZ variant in the product's place,
+ * followed by the dZ launches (the sum over the row tiles, the order-Mz part, the finishing
+ * step), against the first workspace, the scratch and the buffer of dZ's partials. short_ws 1 / 2
+ * as there; 3: the buffer of the partials one element short (the finishing step's store leaves
+ * it); 0: as allocated. Not in the reference. */
+int gaplac_plan_check_sparse_grad_z(int64_t N, int64_t Mz, int32_t T, int32_t spw, int32_t short_ws,
+                                    int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* Host-only accounting of the single-GPU schedule for order N (GAPLAC_SPW = spw,
  * GAPLAC_PAIR_DEPTH = depth (0: auto), band extension pair_ext (0/1), GAPLAC_PAIR_M =
  * pair_m): every tile column gets every earlier panel column exactly once, in order, before

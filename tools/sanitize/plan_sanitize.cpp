@@ -15,6 +15,8 @@
 //   gaplac_plan_check_sparse_grad - the same for gaplac_sparse_elbo_grad: the value's stages,
 //                                the order-Mz launches against the gradient's scratch, alpha and
 //                                the product kernel against the first workspace and the scratch;
+//   gaplac_plan_check_sparse_grad_z - the same for gaplac_sparse_elbo_grad_z: the product's dZ
+//                                variant and the dZ launches, the partials as a third region;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -137,6 +139,20 @@ int main() {
                        short_ws, (long long)N, (long long)Mz);
             }
     EXPECT(gaplac_plan_check_sparse_grad(10, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "sparse grad: Mz = 0 accepted");
+    // the same with dZ: the product's dZ variant, the sums over the row tiles, the order-Mz part and
+    // the finishing step, the buffer of the partials as a third region; then that one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t Mz : {1, 5, 127, 128, 129, 257, 513, 1024, 4096})
+            for (int64_t N : {1, 5, 127, 128, 129, 300, 700, 1000, 2000, 2051, 16384, 262144}) {
+                const int T = 1 + (int)((N + Mz) % 16);
+                int rc = gaplac_plan_check_sparse_grad_z(N, Mz, T, spw, 0, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && a > 0 && b == 0, "plan_check_sparse_grad_z N=%lld Mz=%lld T=%d spw=%d: rc %d violations %lld %s",
+                       (long long)N, (long long)Mz, T, spw, rc, (long long)b, msg);
+                rc = gaplac_plan_check_sparse_grad_z(N, Mz, T, spw, 3, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && b >= 1, "negative control (sparse grad z, short_ws 3) N=%lld Mz=%lld not reported",
+                       (long long)N, (long long)Mz);
+                ++checks;
+            }
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
