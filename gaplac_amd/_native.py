@@ -43,6 +43,9 @@ EXPORTED = (
     "gaplac_sparse_elbo_grad",
     "gaplac_sparse_elbo_grad_z",
     "gaplac_sparse_posterior_mean_var",
+    "gaplac_sparse_posterior_mean_cov",
+    "gaplac_sparse_posterior_rand",
+    "gaplac_sparse_posterior_logpdf",
     "gaplac_sparse_split",
     "gaplac_gram",
     "gaplac_gram_time",
@@ -56,6 +59,7 @@ EXPORTED = (
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
     "gaplac_plan_check_sparse_grad_z",
+    "gaplac_plan_check_sparse_joint",
     "gaplac_dist_create",
     "gaplac_dist_destroy",
     "gaplac_dist_last_error",
@@ -188,6 +192,13 @@ def load() -> ctypes.CDLL:
     lib.gaplac_plan_check_sparse_grad_z.argtypes = [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int64),
                                                     POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_sparse_posterior_mean_var.argtypes = sparse + [c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+    # (the sparse joint entries: the head of sparse_posterior_mean_var, then noise_s)
+    sjoint = sparse + [c_int64, c_void_p, c_int64, c_double]
+    lib.gaplac_sparse_posterior_mean_cov.argtypes = sjoint + [c_void_p, c_void_p, c_int64]
+    lib.gaplac_sparse_posterior_rand.argtypes = sjoint + [c_int64, c_void_p, c_int64, c_void_p, c_int64]
+    lib.gaplac_sparse_posterior_logpdf.argtypes = sjoint + [c_int64, c_void_p, c_int64, c_void_p, _DP, c_void_p]
+    lib.gaplac_plan_check_sparse_joint.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int32, c_int32,
+                                                   POINTER(c_int64), POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_sparse_split.argtypes = [c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]
     lib.gaplac_plan_check_sparse.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
                                              POINTER(c_int64), c_char_p, c_int64]

@@ -261,6 +261,39 @@ class ApproxPosteriorGP:
     def var(self, x):
         return self.mean_and_var(x)[1]
 
+    def __call__(self, x, noise=0.0):
+        """AbstractGPs' fp(xs, σ²): the approximate posterior at the rows of x, jointly, with
+        observation variance noise there."""
+        return FiniteApproxPosteriorGP(self, x, noise)
+
+
+class FiniteApproxPosteriorGP(FinitePosteriorGP):
+    """posterior(VFE(f(z)), fx, y)(xs, noise): the finite-dimensional Gaussian of the
+    inducing-point posterior (gaplac.h, the sparse joint entries). A FinitePosteriorGP to
+    mean_and_cov, cov, rand and logpdf: the same gate and shape checks, one library call per
+    query."""
+
+    def __init__(self, f: ApproxPosteriorGP, x, noise=0.0):
+        X = np.asarray(x, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        self.f = f
+        self.x = np.asfortranarray(X)
+        self.noise = float(noise)
+
+    def _args(self):
+        return (*self.f._args, self.x, self.noise)
+
+    def mean_and_cov(self, ctx=None):
+        _gate()
+        return self._ctx(ctx).sparse_posterior_mean_cov(*self._args())
+
+    def _rand(self, z, ctx):
+        return self._ctx(ctx).sparse_posterior_rand(*self._args(), z)
+
+    def _logpdf(self, ys, ctx, full):
+        return self._ctx(ctx).sparse_posterior_logpdf(*self._args(), ys, full=full)
+
 
 def posterior(*args, ctx: backend.Context | None = None):
     """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8), or

@@ -446,6 +446,69 @@ class Context:
         self._check(rc)
         return mean, var
 
+    def _sparse_joint_head(self, X, terms, noise, y, Z, jitter, Xs, noise_s):
+        """The argument head the three sparse joint entries share (after self.h)."""
+        head, keep, D = self._sparse_head(X, terms, noise, y, Z, jitter)
+        Xsc = _colmajor(Xs)
+        Ms = Xsc.shape[0]
+        if Xsc.shape[1] != D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {D}")
+        head = head + (Ms, Xsc.ctypes.data_as(c_void_p), max(Ms, 1), float(noise_s))
+        return head, keep + (Xsc,), Ms
+
+    def sparse_posterior_mean_cov(self, X, terms, noise: float, y, Z, jitter: float, Xs, noise_s: float = 0.0):
+        """(mean, cov) of the approximate posterior given y, jointly at the rows of Xs with
+        observation variance noise_s there (gaplac_sparse_posterior_mean_cov): cov is the full
+        symmetric Ms x Ms matrix."""
+        head, keep, Ms = self._sparse_joint_head(X, terms, noise, y, Z, jitter, Xs, noise_s)
+        mean = np.empty(Ms, dtype=np.float64)
+        cov = np.empty((Ms, Ms), dtype=np.float64, order="F")
+        mb = mean if Ms else np.empty(1)  # (an empty result still passes valid pointers)
+        cb = cov if Ms else np.empty(1)
+        rc = self.lib.gaplac_sparse_posterior_mean_cov(self.h, *head, mb.ctypes.data_as(c_void_p),
+                                                       cb.ctypes.data_as(c_void_p), max(Ms, 1))
+        self._check(rc)
+        return mean, cov
+
+    def sparse_posterior_rand(self, X, terms, noise: float, y, Z, jitter: float, Xs, noise_s: float, E):
+        """m 1^T + L* E (gaplac_sparse_posterior_rand): one joint draw of the approximate posterior
+        at the rows of Xs per column of the standard-normal matrix E (Ms x R). Returns Ms x R
+        (column-major)."""
+        head, keep, Ms = self._sparse_joint_head(X, terms, noise, y, Z, jitter, Xs, noise_s)
+        Ec = np.asarray(E, dtype=np.float64)
+        if Ec.ndim != 2:
+            raise ArgumentError(f"E must be a matrix (Ms x R), got {Ec.ndim} dimension(s)")
+        Ec = np.asfortranarray(Ec)
+        if Ec.shape[0] != Ms:
+            raise ArgumentError(f"rows of E ({Ec.shape[0]}) != Ms ({Ms})")
+        R = Ec.shape[1]
+        out = np.empty((Ms, R), dtype=np.float64, order="F")
+        buf = out if out.size else np.empty(1)
+        rc = self.lib.gaplac_sparse_posterior_rand(self.h, *head, R, Ec.ctypes.data_as(c_void_p), max(Ms, 1),
+                                                   buf.ctypes.data_as(c_void_p), max(Ms, 1))
+        self._check(rc)
+        return out
+
+    def sparse_posterior_logpdf(self, X, terms, noise: float, y, Z, jitter: float, Xs, noise_s: float, Ys,
+                                full: bool = False):
+        """logpdf of every column of Ys (Ms x R) under the joint approximate posterior at the rows
+        of Xs (gaplac_sparse_posterior_logpdf): an array of R, or (logpdf[R], logdet, quad[R]) with
+        full=True."""
+        head, keep, Ms = self._sparse_joint_head(X, terms, noise, y, Z, jitter, Xs, noise_s)
+        Yc = np.asarray(Ys, dtype=np.float64)
+        if Yc.ndim != 2:
+            raise ArgumentError(f"Ys must be a matrix (Ms x R), got {Yc.ndim} dimension(s)")
+        Yc = np.asfortranarray(Yc)
+        if Yc.shape[0] != Ms:
+            raise ArgumentError(f"rows of Ys ({Yc.shape[0]}) != Ms ({Ms})")
+        R = Yc.shape[1]
+        lp, ld, q = self._multi_outputs(R)
+        rc = self.lib.gaplac_sparse_posterior_logpdf(self.h, *head, R, Yc.ctypes.data_as(c_void_p), max(Ms, 1),
+                                                     lp.ctypes.data_as(c_void_p), byref(ld),
+                                                     q.ctypes.data_as(c_void_p))
+        self._check(rc)
+        return (lp[:R], ld.value, q[:R]) if full else lp[:R]
+
     def sparse_split(self, N: int, Mz: int):
         """(chunks, chunk_rows) of the product over the N rows (gaplac_sparse_split)."""
         chunks, rows = c_int64(), c_int64()

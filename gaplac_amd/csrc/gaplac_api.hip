@@ -234,6 +234,13 @@ struct gaplac_ctx {
     // the evaluation is described as on_prebuilt(): it finds its matrix already built.
     double* B = nullptr;
     size_t B_elems = 0;
+    // Joint covariance of the inducing-point posterior: the order-Ms workspace that
+    // sparse_post_cov_kernel fills and the third factorisation runs in (both others are live by
+    // then), and the tile-aligned copy of the a rows
+    double* C = nullptr;
+    size_t C_elems = 0;
+    double* sj_rows = nullptr;
+    size_t sj_rows_elems = 0;
     // Inducing-point approximation: y on the device and the chunk partials of S
     double* sp_y = nullptr;
     size_t sp_y_elems = 0;
@@ -336,7 +343,8 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        large(&c->B, &c->B_elems), large(&c->sp_y, &c->sp_y_elems),
                        large(&c->sp_part, &c->sp_part_elems), large(&c->sg, &c->sg_elems),
                        large(&c->sg_dinv, &c->sg_dinv_elems), large(&c->sg_v, &c->sg_v_elems),
-                       large(&c->sgz, &c->sgz_elems)};
+                       large(&c->sgz, &c->sgz_elems), large(&c->C, &c->C_elems),
+                       large(&c->sj_rows, &c->sj_rows_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -1717,13 +1725,17 @@ int joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t 
 }
 
 // The second factorisation runs in B: A and B change places for as long as this lives.
+// (Given another workspace, A changes places with that one: the sparse joint entries' third, §10.11.)
 struct WsSwap {
     gaplac_ctx* c;
-    explicit WsSwap(gaplac_ctx* ctx) : c(ctx) { flip(); }
+    double** w;
+    size_t* w_elems;
+    explicit WsSwap(gaplac_ctx* ctx) : WsSwap(ctx, &ctx->B, &ctx->B_elems) {}
+    WsSwap(gaplac_ctx* ctx, double** other, size_t* other_elems) : c(ctx), w(other), w_elems(other_elems) { flip(); }
     ~WsSwap() { flip(); }
     void flip() {
-        std::swap(c->A, c->B);
-        std::swap(c->A_elems, c->B_elems);
+        std::swap(c->A, *w);
+        std::swap(c->A_elems, *w_elems);
     }
 };
 
@@ -2316,6 +2328,211 @@ int sparse_posterior_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
     if (out_var)
         HIPCK(ctx, hipMemcpyAsync(out_var, ctx->pvar + N, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+// ---- joint covariance, draws and logpdf of the inducing-point posterior ----
+// The third workspace C of order Ms with R responses in rt riding tile rows (R = 0: none), and the
+// tile-aligned copy of the a rows (Np columns, leading dimension ldr), for the entries and for
+// gaplac_plan_check_sparse_joint alike.
+struct SparseJointDims {
+    int rt;
+    int64_t Msp, ldc, ldr;
+};
+SparseJointDims sparse_joint_dims(int64_t Ms, int64_t R) {
+    SparseJointDims j;
+    j.rt = (int)((R + NB - 1) / NB);
+    j.Msp = round_up(Ms + 1, NB);
+    j.ldc = j.Msp + (int64_t)NB * j.rt;
+    j.ldr = round_up(Ms, NB);
+    return j;
+}
+
+// The a rows of stage 1 (A: the first workspace) into their tile-aligned copy.
+void sparse_joint_copy_launches(hipStream_t s, const SparseDims& d, const SparseJointDims& j, int64_t N, int64_t Mz,
+                                int64_t Ms, const double* A, double* rows) {
+    launch_sparse_rows_copy(s, A, d.lda, d.Np, N, Mz, Ms, rows, j.ldr);
+}
+// After stage 3 and the mean's reduction (Bw: the second workspace): the augmented matrix of Sigma*
+// into C (row Ms, the v row, carries the mean: its results are not used), and with `mirror` its
+// upper triangle from the lower. Run by the entries and walked dry by the plan check (Xs, mean and
+// dtp may be null there).
+void sparse_joint_cov_launches(hipStream_t s, const SparseDims& d, const SparseJointDims& j, int64_t Mz, int64_t Ms,
+                               double* Bw, const double* rows, double* C, const double* Xs, int64_t ldxs,
+                               const double* mean, const TermPack* dtp, double noise, bool mirror) {
+    launch_sparse_post_cov(s, Bw, d.ldb, d.Np, Mz, Ms, rows, j.ldr, C, j.ldc, Xs, ldxs, mean, dtp, noise);
+    if (mirror) launch_mirror_lower(s, C, j.ldc, Ms);
+}
+
+// Argument checks the three entries share, after their own (sizes and output pointers).
+int sparse_joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise,
+                       const double* y, int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms,
+                       const double* Xs, int64_t ldxs, double noise_s) {
+    int rc = sparse_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs);
+    if (rc) return rc;
+    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
+        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
+    return 0;
+}
+
+// The three stages of gaplac_sparse_posterior_mean_var (the mean in ctx->pmean, by the same
+// launches), then the augmented matrix of Sigma* into ctx->C, laid out for a factorisation of
+// order Ms with R riding responses (mirror: mirrored into a full matrix). tp comes in with the
+// training noise and leaves with noise_s (the pack of the third factorisation, also in ctx->dtp).
+// On return the workspaces are back in their places: the caller rotates C in for its factorisation.
+int sparse_joint_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, TermPack& tp,
+                        const double* y, int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms,
+                        const double* Xs, int64_t ldxs, double noise_s, int64_t R, bool mirror) {
+    int rc;
+    const double noise = tp.noise;
+    if ((rc = sparse_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, nullptr))) return rc;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
+    const SparseJointDims j = sparse_joint_dims(Ms, R);
+    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)Mz * (size_t)Ms))) return rc;
+    if ((rc = ensure(ctx, &ctx->gpart, &ctx->gpart_elems, 2 * (size_t)Ms * (size_t)((Mz + 511) / 512)))) return rc;
+    if ((rc = ensure(ctx, &ctx->sj_rows, &ctx->sj_rows_elems, (size_t)d.Np * (size_t)j.ldr))) return rc;
+    if ((rc = ensure(ctx, &ctx->C, &ctx->C_elems, (size_t)j.ldc * (size_t)j.Msp))) return rc;
+    if ((rc = guarded_on(ctx, ctx->A, ctx->A_elems, ctx->sj_rows, ctx->sj_rows_elems, [&] {
+             sparse_rows_launches(ctx->s_main, d, N, Mz, Ms, ctx->A, ctx->dY);
+             sparse_joint_copy_launches(ctx->s_main, d, j, N, Mz, Ms, ctx->A, ctx->sj_rows);
+         })))
+        return rc;
+    WsSwap swap(ctx);  // ctx->A is the workspace of S until this returns
+    EvalResult r2;
+    if ((rc = joint_factor(ctx, Mz, D, tp, ExtraRows::responses(Ms, ctx->dY, Mz).on_prebuilt(), &r2, SPARSE_S)))
+        return rc;
+    if ((rc = guarded(ctx, false, [&] {
+             sparse_post_launches(ctx->s_main, d, Mz, Ms, noise, ctx->A, ctx->gpart, ctx->pmean, ctx->pvar + N);
+         })))
+        return rc;
+    tp.noise = noise_s;
+    *ctx->htp = tp;  // (stage 3 has retired: eval_device waited for it)
+    HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, ctx->s_main));
+    // <trace path>.sj: "Mz Ms ms" of the covariance launches alone
+    return trace_timed(ctx, ".sj", Mz, Ms, [&] {
+        return guarded_on(
+            ctx, ctx->A, ctx->A_elems, ctx->C, ctx->C_elems,
+            [&] {
+                sparse_joint_cov_launches(ctx->s_main, d, j, Mz, Ms, ctx->A, ctx->sj_rows, ctx->C, ctx->dXs + N, N + Ms,
+                                          ctx->pmean, ctx->dtp, noise, mirror);
+            },
+            ctx->sj_rows, ctx->sj_rows_elems);
+    });
+}
+
+int sparse_posterior_mean_cov_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                   const gaplac_term* terms, double noise, const double* y, int64_t Mz,
+                                   const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
+                                   int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (Ms < 0 || (out_cov && ldc < Ms)) return set_err(ctx, GAPLAC_E_ARG, "Ms = %lld < 0 or ldc < Ms", (long long)Ms);
+    for (int64_t j = 0; j < Ms; ++j) {  // (rows Ms .. ldc-1 of out_cov are the caller's)
+        if (out_mean) out_mean[j] = NAN;
+        if (out_cov)
+            for (int64_t i = 0; i < Ms; ++i) out_cov[j * ldc + i] = NAN;
+    }
+    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (Ms == 0) return 0;
+    if (N == 0 || Mz == 0) {  // no data, or Q = 0: the prior
+        if (out_cov && (rc = gaplac_gram(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, out_cov, ldc))) return rc;
+        for (int64_t j = 0; j < Ms && out_mean; ++j) out_mean[j] = 0.0;
+        return 0;
+    }
+    tp.noise = noise;
+    if (!out_cov) {  // the mean alone: the three stages of gaplac_sparse_posterior_mean_var
+        return sparse_posterior_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, out_mean,
+                                     nullptr);
+    }
+    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, 0, true)))
+        return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->C, (size_t)sparse_joint_dims(Ms, 0).ldc * 8,
+                                (size_t)Ms * 8, (size_t)Ms, hipMemcpyDeviceToHost, ctx->s_main));
+    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+int sparse_posterior_rand_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                               const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                               int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs, double noise_s,
+                               int64_t R, const double* E, int64_t lde, double* out, int64_t ldo) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (Ms < 0 || R < 0 || !out || lde < Ms || ldo < Ms || (R > 0 && Ms > 0 && !E))
+        return set_err(ctx, GAPLAC_E_ARG, "Ms < 0, R < 0, E / out NULL, or lde / ldo < Ms");
+    for (int64_t r = 0; r < R; ++r)  // (rows Ms .. ldo-1 of out are the caller's)
+        for (int64_t i = 0; i < Ms; ++i) out[r * ldo + i] = NAN;
+    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (Ms == 0 || R == 0) return 0;
+    if (N == 0 || Mz == 0)  // the prior at the test points
+        return gaplac_rand_multi(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, R, E, lde, out, ldo);
+    if ((R + NB - 1) / NB > 65535)
+        return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
+    tp.noise = noise;
+    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, 0, false)))
+        return rc;
+    const int64_t Msp = sparse_joint_dims(Ms, 0).Msp;
+    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Msp * (size_t)R))) return rc;
+    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)Ms * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Msp * 8, E, (size_t)lde * 8, (size_t)Ms * 8, (size_t)R,
+                                hipMemcpyHostToDevice, ctx->s_main));
+    WsSwap third(ctx, &ctx->C, &ctx->C_elems);  // from here on ctx->A is the order-Ms workspace
+    EvalResult r3;
+    if ((rc = joint_factor(ctx, Ms, D, tp, ExtraRows{}.on_prebuilt(), &r3))) return rc;
+    if ((rc = guarded(ctx, false,
+                      [&] { draws_launches(ctx->s_main, ctx->A, Msp, Ms, ctx->dZ, R, ctx->dO, ctx->pmean); })))
+        return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)Ms * 8, (size_t)Ms * 8, (size_t)R,
+                                hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+int sparse_posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                 const gaplac_term* terms, double noise, const double* y, int64_t Mz,
+                                 const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
+                                 int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
+                                 double* out_logpdf, double* out_logdet, double* out_quad) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (Ms < 0 || R < 0 || !out_logpdf || ldys < Ms || (R > 0 && Ms > 0 && !Ys))
+        return set_err(ctx, GAPLAC_E_ARG, "Ms < 0, R < 0, Ys / out_logpdf NULL, or ldys < Ms");
+    if (Ms > 0 && R > 0) {  // (an empty call writes nothing)
+        for (int64_t r = 0; r < R; ++r) {
+            out_logpdf[r] = NAN;
+            if (out_quad) out_quad[r] = NAN;
+        }
+        if (out_logdet) *out_logdet = NAN;
+    }
+    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
+    if (rc) return rc;
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    if (Ms == 0 || R == 0) return 0;
+    if (N == 0 || Mz == 0)  // the prior at the test points
+        return gaplac_logpdf_multi(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, R, Ys, ldys, out_logpdf, out_logdet,
+                                   out_quad);
+    if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
+        return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
+    tp.noise = noise;
+    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, R, false)))
+        return rc;
+    // ctx->dY held the transposed a rows for stage 3, which has retired: the responses take it over
+    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)Ms * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)Ms * 8, Ys, (size_t)ldys * 8, (size_t)Ms * 8, (size_t)R,
+                                hipMemcpyHostToDevice, ctx->s_main));
+    WsSwap third(ctx, &ctx->C, &ctx->C_elems);
+    // the rows hold (Ys - m 1^T)^T and ride along as the responses of gaplac_logpdf_multi do
+    EvalResult r3;
+    if ((rc = joint_factor(ctx, Ms, D, tp, ExtraRows::responses(R, ctx->dY, Ms, ctx->pmean).on_prebuilt(), &r3)))
+        return rc;
+    if (out_logdet) *out_logdet = r3.logdet;
+    if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
+    HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -3000,6 +3217,31 @@ int gaplac_sparse_elbo_grad_z(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
                                  out_dparam, out_dnoise, out_djitter, out_dZ, lddz);
 }
 
+int gaplac_sparse_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                     const gaplac_term* terms, double noise, const double* y, int64_t Mz,
+                                     const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
+                                     int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
+    return sparse_posterior_mean_cov_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs,
+                                          noise_s, out_mean, out_cov, ldc);
+}
+
+int gaplac_sparse_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                 const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
+                                 int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs,
+                                 double noise_s, int64_t R, const double* E, int64_t lde, double* out, int64_t ldo) {
+    return sparse_posterior_rand_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s,
+                                      R, E, lde, out, ldo);
+}
+
+int gaplac_sparse_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                   const gaplac_term* terms, double noise, const double* y, int64_t Mz,
+                                   const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
+                                   int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
+                                   double* out_logpdf, double* out_logdet, double* out_quad) {
+    return sparse_posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs,
+                                        noise_s, R, Ys, ldys, out_logpdf, out_logdet, out_quad);
+}
+
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {
     if (N < 0 || Mz < 0 || !out_chunks || !out_chunk_rows) return GAPLAC_E_ARG;
     sparse_split(N, Mz, out_chunks, out_chunk_rows);
@@ -3115,6 +3357,67 @@ int gaplac_plan_check_sparse_grad_z(int64_t N, int64_t Mz, int32_t T, int32_t sp
                                     int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) {
     if (T < 1 || T > GAPLAC_MAX_TERMS || short_ws < 0 || short_ws > 3) return GAPLAC_E_ARG;
     return plan_sparse_grad(N, Mz, T, spw, short_ws, out_launches, out_violations, msg, msglen);
+}
+
+// Host-only walk of the sparse joint entries (§10.11, no device needed): gaplac_plan_check_sparse
+// with Ms test points (the three stages and the mean's reduction), the copy of the a rows against
+// the first workspace, the covariance launches (zeroing, sparse_post_cov_kernel, the mirroring
+// pass) against the second and third, and the prebuilt factorisation of order Ms in the third,
+// with R > 0 carrying R riding rows (gaplac_sparse_posterior_logpdf), else plain
+// (gaplac_sparse_posterior_rand). The launches between the evaluations are the entries' own
+// functions, run dry; the copy of the a rows (never short) is a guarded region of both. Gaps
+// against the entries: the walk takes the copy after the first two factorisations (the entries
+// before the second), the mirroring pass always (the entries for gaplac_sparse_posterior_mean_cov
+// only), and gaplac_sparse_posterior_rand's draws_launches are in no walk.
+// short_ws 1 / 2 / 3: that workspace one element short (negative controls).
+int gaplac_plan_check_sparse_joint(int64_t N, int64_t Mz, int64_t Ms, int64_t R, int32_t spw, int32_t short_ws,
+                                   int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || Mz < 1 || Ms < 1 || R < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 3) return GAPLAC_E_ARG;
+    if ((N + Ms + NB - 1) / NB > 65535 || (R + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
+    int64_t l0 = 0, v0 = 0;
+    int rc = gaplac_plan_check_sparse(N, Mz, Ms, spw, short_ws == 3 ? 0 : short_ws, &l0, &v0, msg, msglen);
+    if (rc) return rc;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
+    const SparseJointDims j = sparse_joint_dims(Ms, R);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    double* const fc = reinterpret_cast<double*>((uintptr_t)1 << 46);
+    double* const fr = reinterpret_cast<double*>((uintptr_t)1 << 47);
+    const int64_t a_elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0), b_elems = d.ldb * d.Np - (short_ws == 2 ? 1 : 0);
+    const int64_t c_elems = j.ldc * j.Msp - (short_ws == 3 ? 1 : 0), r_elems = d.Np * j.ldr;
+    LaunchGuard g1, g2, g3;
+    g1.base = fa;
+    g1.elems = a_elems;
+    g1.base2 = fr;
+    g1.elems2 = r_elems;
+    g1.dry = true;
+    {
+        GuardScope scope(&g1);
+        sparse_joint_copy_launches(nullptr, d, j, N, Mz, Ms, fa, fr);
+    }
+    g2.base = fb;
+    g2.elems = b_elems;
+    g2.base2 = fc;
+    g2.elems2 = c_elems;
+    g2.base3 = fr;
+    g2.elems3 = r_elems;
+    g2.dry = true;
+    {
+        GuardScope scope(&g2);
+        sparse_joint_cov_launches(nullptr, d, j, Mz, Ms, fb, fr, fc, nullptr, 0, nullptr, nullptr, 1.0, true);
+    }
+    gaplac_ctx c3;
+    c3.spw = spw;
+    const ExtraRows rows = R > 0 ? ExtraRows::responses(R, nullptr, 0) : ExtraRows{};
+    rc = dry_walk(c3, Ms, rows.on_prebuilt(), g3, short_ws == 3 ? 1 : 0);
+    if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
+    if (out_launches) *out_launches = l0 + g1.launches + g2.launches + g3.launches;
+    if (out_violations) *out_violations = v0 + g1.violations + g2.violations + g3.violations;
+    if (msg && msglen > 0 && v0 == 0) {
+        const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.first;
+        std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+    }
+    return rc;
 }
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior

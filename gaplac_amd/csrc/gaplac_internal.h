@@ -367,6 +367,20 @@ void launch_rows_to_matrix(hipStream_t s, const double* A, int64_t lda, int64_t 
 // row): mean_j = c_j . u, var_j += noise |c_j|^2 (partial: 2 * ceil(Mz/512) * Ms doubles).
 void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t Mz, int64_t Ms, double noise,
                         double* partial, double* mean, double* var);
+// ---- joint covariance of the inducing-point posterior ----
+// R (Np columns, leading dimension ldr = 128 ceil(Ms / 128)) = the riding rows row0 .. row0 + Ms - 1
+// of A's columns k < Mz, tile-aligned and zero-padded (rows >= Ms, columns >= Mz). Checked against
+// the guard's first allocation (A) and its second (R).
+void launch_sparse_rows_copy(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t row0, int64_t Mz,
+                             int64_t Ms, double* R, int64_t ldr);
+// After the second factorisation and launch_sparse_post (Bw: its workspace, leading dimension ldb,
+// the Ms rows b_j^T below the factor): zeroes the b rows' columns [Mz, Np), then C = the augmented
+// matrix of Sigma* = gram(Xs, noise_s) - A^T A + noise B^T B for a factorisation of order Ms (lower
+// tiles, leading dimension ldc >= roundup(Ms+1, 128), row Ms = v, zero padding). dtp: the pack with
+// noise = noise_s. Checked against the guard's first allocation (Bw), its second (C) and its third (R).
+void launch_sparse_post_cov(hipStream_t s, double* Bw, int64_t ldb, int64_t Np, int64_t Mz, int64_t Ms,
+                            const double* R, int64_t ldr, double* C, int64_t ldc, const double* Xs, int64_t ldxs,
+                            const double* v, const TermPack* dtp, double noise);
 // ---- gradient of the inducing-point bound ----
 // G: a column storage of nt tile columns (leading dimension ld >= 2 nt 128) holding a factor in
 // tile rows 0 .. nt-1 and identity rows (launch_init_identity_rows, W = nt) in tile rows nt ..

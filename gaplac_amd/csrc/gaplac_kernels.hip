@@ -3000,6 +3000,91 @@ __global__ __launch_bounds__(256) void sparse_post_finish_kernel(const double* _
 }
 
 // ---------------------------------------------------------------------------------
+// Joint covariance of the inducing-point posterior (AbstractGPs mean_and_cov /
+// rand / logpdf of posterior(VFE(f(z)), fx, y)(xs, noise_s)). After the three stages of
+// gaplac_sparse_posterior_mean_var the rows a_j^T = (L^{-1} K(Z, xs_j))^T lie below the first
+// factor (riding rows N .. N + Ms - 1 of the first workspace) and the rows b_j^T = (L_S^{-1} a_j)^T
+// below the second (riding rows 0 .. Ms - 1 of the second workspace):
+//   Sigma* = gram(Xs, noise_s) - A^T A + noise B^T B,  A = [a_j], B = [b_j]  (Mz x Ms),
+// written as the augmented matrix of a third factorisation (order Ms) into a third workspace.
+// ---------------------------------------------------------------------------------
+
+// R[k ldr + j] = a_j[k] = A[k lda + Np + row0 + j] for j < Ms, k < Mz, and 0 for the other j < ldr,
+// k < Np: the a rows start at riding row row0 = N, which is no multiple of the tile (and for odd N
+// only 8-byte aligned, while tile_mma_neg stages with 16-byte LDS-DMA loads), so the product reads
+// this tile-aligned, zero-padded copy. blockIdx.y strides over the columns k.
+__global__ __launch_bounds__(256) void sparse_rows_copy_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                               int64_t row0, int64_t Mz, int64_t Ms,
+                                                               double* __restrict__ R, int64_t ldr) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= ldr) return;
+    for (int64_t k = blockIdx.y; k < Np; k += gridDim.y)
+        R[k * ldr + j] = (j < Ms && k < Mz) ? A[k * lda + Np + row0 + j] : 0.0;
+}
+
+// post_cov_kernel's counterpart: one workgroup = one 128x128 lower tile (bi >= bj) of C, the
+// augmented matrix of order Ms (row Ms = v, the mean; the diagonal rule in the padding). The tile
+// starts as the test points' Gram tile (gram_tile over Xs, the pack's noise = noise_s), built in
+// the MMA staging LDS and stored. Then, with ONE accumulator set and tile_mma_neg unchanged:
+//   1. acc = 0; acc -= b_i . b_j over k = 0 .. Np-1 ascending   (the rows below the second factor,
+//      Bw: row j at Bw[k ldb + Np + j]; columns k >= Mz zeroed by zero_xrow_cols_kernel first)
+//   2. acc = gram - noise * acc                                  (read back from the stored tile)
+//   3. acc -= a_i . a_j over k = 0 .. Np-1 ascending             (the tile-aligned copy R, ld ldr)
+// and the tile is stored again. One accumulator chain per element, K never split, every step in a
+// fixed order: an entry does not depend on Ms or on where its points stand, and a call is bitwise
+// repeatable. Tile row mt (Ms a multiple of 128: the v row and the padding only) has no rows in
+// either block and stays as gram_tile wrote it.
+__global__ __launch_bounds__(256, 2) void sparse_post_cov_kernel(const double* __restrict__ Bw, int64_t ldb,
+                                                                 const double* __restrict__ R, int64_t ldr,
+                                                                 int64_t Np, int mt, double* __restrict__ C,
+                                                                 int64_t ldc, int64_t Ms,
+                                                                 const double* __restrict__ Xs, int64_t ldxs,
+                                                                 const double* __restrict__ v,
+                                                                 const TermPack* __restrict__ tpp, double noise) {
+    __shared__ MmaLds sm;
+    int bi, bj;
+    tri_index(blockIdx.x, bi, bj);
+    gram_tile(C + (int64_t)bj * NB * ldc, ldc, Ms, Xs, ldxs, v, tpp, bi, bj, reinterpret_cast<double*>(&sm));
+    if (bi >= mt) return;
+    __syncthreads();  // the tile's stores are complete (and the LDS free) before the staging reuses it
+    double* __restrict__ Ct = C + (int64_t)bj * NB * ldc + (int64_t)bi * NB;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    const int wi = w & 1, wj = w >> 1;
+    const bool active = !(bi == bj && wj > wi);
+    const int fr = lane >> 4, fc = lane & 15;
+    d4 acc[4][4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj) acc[mi][mj] = d4{0.0, 0.0, 0.0, 0.0};
+    tile_mma_neg<KB>(Bw + Np + (int64_t)bi * NB, Bw + Np + (int64_t)bj * NB, ldb, (int)Np, active, acc, sm);
+    if (active) {
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const double* Ci = Ct + 64 * wi + 16 * mi + fc;
+#pragma unroll
+            for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+                for (int rg = 0; rg < 4; ++rg)
+                    acc[mi][mj][rg] = Ci[(int64_t)(64 * wj + 16 * mj + fr + 4 * rg) * ldc] - noise * acc[mi][mj][rg];
+        }
+    }
+    // (tile_mma_neg ends on a barrier: the staging buffer is free)
+    tile_mma_neg<KB>(R + (int64_t)bi * NB, R + (int64_t)bj * NB, ldr, (int)Np, active, acc, sm);
+    if (!active) return;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        double* Ci = Ct + 64 * wi + 16 * mi + fc;
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int rg = 0; rg < 4; ++rg)
+                Ci[(int64_t)(64 * wj + 16 * mj + fr + 4 * rg) * ldc] = acc[mi][mj][rg];
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Gradient of the inducing-point bound. With V^T still below the first
 // factor and L_S in the second workspace:
 //   c = L_S^{-T} u, ctil = L^{-T} c, alpha = (y - V^T c) / noise, Phi = I / noise - S^{-1},
@@ -4834,6 +4919,36 @@ void launch_sparse_post(hipStream_t s, const double* A, int64_t lda, int64_t Np,
                                                                                              pv);
     sparse_post_finish_kernel<<<dim3((unsigned)((Ms + 255) / 256)), dim3(256), 0, s>>>(pm, pv, Ms, nk, noise, mean,
                                                                                       var);
+}
+
+void launch_sparse_rows_copy(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t row0, int64_t Mz,
+                             int64_t Ms, double* R, int64_t ldr) {
+    if (Mz <= 0 || Ms <= 0) return;
+    const bool a_ok = guard_launch("sparse_rows_copy_kernel (riding rows)", A, Np + row0,
+                                   (Mz - 1) * lda + Np + row0 + Ms);
+    const bool r_ok = guard_launch("sparse_rows_copy_kernel", R, 0, Np * ldr, 1);
+    if (!a_ok || !r_ok || ldr < Ms) return;
+    sparse_rows_copy_kernel<<<dim3((unsigned)((ldr + 255) / 256), (unsigned)std::min<int64_t>(Np, 65535)), dim3(256), 0,
+                              s>>>(A, lda, Np, row0, Mz, Ms, R, ldr);
+}
+
+void launch_sparse_post_cov(hipStream_t s, double* Bw, int64_t ldb, int64_t Np, int64_t Mz, int64_t Ms,
+                            const double* R, int64_t ldr, double* C, int64_t ldc, const double* Xs, int64_t ldxs,
+                            const double* v, const TermPack* dtp, double noise) {
+    if (Mz <= 0 || Ms <= 0) return;
+    const int64_t mt = (Ms + NB - 1) / NB, Mp = (Ms + NB) / NB * NB, ntc = Mp / NB;
+    const int64_t rows = mt * NB;
+    // the kernel sums whole staging chunks up to Np: the columns [Mz, Np) of the b rows are zeroed first
+    if (guard_launch("zero_xrow_cols_kernel (sparse)", Bw, Mz * ldb + Np, (Np - 1) * ldb + Np + rows))
+        zero_xrow_cols_kernel<<<dim3((unsigned)((rows + 255) / 256), (unsigned)(Np - Mz)), dim3(256), 0, s>>>(
+            Bw, ldb, Np, Mz, rows);
+    // reads the b rows of every column of Bw and the copy of the a rows; writes C's lower tiles
+    const bool b_ok = guard_launch("sparse_post_cov_kernel (b rows)", Bw, Np, (Np - 1) * ldb + Np + rows);
+    const bool c_ok = guard_launch("sparse_post_cov_kernel", C, 0, tiles_end(ldc, ntc - 1, ntc - 1), 1);
+    const bool r_ok = guard_launch("sparse_post_cov_kernel (a rows)", R, 0, (Np - 1) * ldr + rows, 2);
+    if (!b_ok || !c_ok || !r_ok || ldr < rows) return;
+    sparse_post_cov_kernel<<<dim3((unsigned)(ntc * (ntc + 1) / 2)), dim3(256), 0, s>>>(Bw, ldb, R, ldr, Np, (int)mt, C,
+                                                                                     ldc, Ms, Xs, ldxs, v, dtp, noise);
 }
 
 void launch_rows_solve(hipStream_t s, double* G, int64_t ld, int nt, const double* Dinv) {

@@ -364,6 +364,59 @@ int gaplac_sparse_elbo_grad_z(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
                               int64_t Mz, const double* Z, int64_t ldz, double jitter,
                               double* out_elbo, double* out_dy, double* out_dparam, double* out_dnoise,
                               double* out_djitter, double* out_dZ, int64_t lddz);
+/* The joint forms of the approximate posterior at the Ms test points, observed with variance
+ * noise_s >= 0. With L, a_j, S, L_S, u as above and b_j = L_S^{-1} a_j:
+ *     m_j    = b_j . u                       (the mean gaplac_sparse_posterior_mean_var returns)
+ *     Sigma* = gram(Xs, terms, noise_s) - A^T A + noise B^T B = L* L*^T,
+ *                                            A = [a_j], B = [b_j]  (Mz x Ms)
+ * where gram(Xs, terms, noise_s) is the test points' own Gram matrix as gaplac_gram builds it
+ * (noise_s on the diagonal; a NOISE term counts on its diagonal and is 0 across point sets). The
+ * three stages of gaplac_sparse_posterior_mean_var (the mean by the same launches), one fp64-MFMA
+ * kernel for Sigma* (per element one accumulator chain: the b products in ascending k from zero,
+ * folded into the Gram entry as gram - noise * acc, then the a products in ascending k; nothing
+ * split, so a call is bitwise repeatable and an entry does not depend on Ms or on where its
+ * points stand) into a third workspace and, for rand / logpdf, a third factorisation, of order
+ * Ms, of the matrix that kernel left in device memory.
+ * Conventions are those of the joint entries and of the sparse entries combined: every output is
+ * NaN-filled first; info > 0 when any of the three Choleskys fails (all outputs stay NaN;
+ * gaplac_last_error names the matrix: the inducing covariance, S, or the test-point covariance
+ * with info = the 1-based leading minor of Sigma*). GAPLAC_E_PARAM for noise <= 0 or jitter < 0
+ * (or non-finite); GAPLAC_E_ARG for noise_s < 0 or non-finite, negative sizes, a leading dimension
+ * below its row count, a NULL matrix of positive size, out / out_logpdf NULL; GAPLAC_E_OOM when
+ * ceil((N + Ms)/128) > 65535, ceil(R/128) > 65535 or the three workspaces do not fit (no
+ * chunking). Ms = 0 or R = 0: 0 after the argument and term checks, nothing written. N = 0 or
+ * Mz = 0: the prior at the test points (mean 0, gaplac_gram, gaplac_rand_multi,
+ * gaplac_logpdf_multi on (Xs, noise_s)). The context stays usable after every failure.
+ *
+ * mean_cov: m (Ms values) and the full symmetric Sigma* (Ms x Ms column-major, leading dimension
+ * ldc; both triangles written, exact mirror images; rows Ms .. ldc-1 untouched). Either output
+ * may be NULL. No third factorisation: an indefinite Sigma* is returned as it is.
+ * Replaces: mean_and_cov(posterior(VFE(f(z, jitter)), f(x, noise), y)(xs, noise_s)) of
+ * AbstractGPs 0.5.12. */
+int gaplac_sparse_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                                     int32_t T, const gaplac_term* terms, double noise, const double* y,
+                                     int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                                     int64_t Ms, const double* Xs, int64_t ldxs, double noise_s,
+                                     double* out_mean, double* out_cov, int64_t ldc);
+/* rand: out = m 1^T + L* E for the Ms x R standard-normal matrix E the caller drew (leading
+ * dimension lde); out is Ms x R (ldo; rows Ms .. ldo-1 untouched). A column's sample depends
+ * neither on R nor on the column's position.
+ * Replaces: rand(rng, posterior(VFE(f(z, jitter)), f(x, noise), y)(xs, noise_s), R). */
+int gaplac_sparse_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                                 int32_t T, const gaplac_term* terms, double noise, const double* y,
+                                 int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                                 int64_t Ms, const double* Xs, int64_t ldxs, double noise_s,
+                                 int64_t R, const double* E, int64_t lde, double* out, int64_t ldo);
+/* logpdf: out_logpdf[r] = -(Ms log 2pi + logdet Sigma* + |L*^{-1} (Ys[:, r] - m)|^2) / 2 for the
+ * Ms x R matrix Ys of held-out responses (ldys); out_logdet (one value) and out_quad (R values)
+ * may be NULL.
+ * Replaces: logpdf(posterior(VFE(f(z, jitter)), f(x, noise), y)(xs, noise_s), Ys). */
+int gaplac_sparse_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                                   int32_t T, const gaplac_term* terms, double noise, const double* y,
+                                   int64_t Mz, const double* Z, int64_t ldz, double jitter,
+                                   int64_t Ms, const double* Xs, int64_t ldxs, double noise_s,
+                                   int64_t R, const double* Ys, int64_t ldys,
+                                   double* out_logpdf, double* out_logdet, double* out_quad);
 /* Host-only: the split of the product for S over the N rows, *out_chunks chunks of
  * *out_chunk_rows rows (the last one ragged), summed in ascending order. A function of (N, Mz)
  * alone. GAPLAC_E_ARG for N < 0, Mz < 0 or a NULL output. Not in the reference. */
@@ -476,6 +529,14 @@ int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t sh
  * it); 0: as allocated. Not in the reference. */
 int gaplac_plan_check_sparse_grad_z(int64_t N, int64_t Mz, int32_t T, int32_t spw, int32_t short_ws,
                                     int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for the sparse joint entries: gaplac_plan_check_sparse with Ms >= 1 test points,
+ * then the tile-aligned copy of the test points' rows against the first workspace, the covariance
+ * launches (with the mirroring pass) against the second and third, and the third factorisation, of
+ * order Ms (R > 0: with R riding rows, as gaplac_sparse_posterior_logpdf; R = 0: plain, as
+ * gaplac_sparse_posterior_rand). short_ws 1 / 2 / 3: the first / second / third workspace one
+ * element short (the negative controls); 0: as allocated. Not in the reference. */
+int gaplac_plan_check_sparse_joint(int64_t N, int64_t Mz, int64_t Ms, int64_t R, int32_t spw, int32_t short_ws,
+                                   int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* Host-only accounting of the single-GPU schedule for order N (GAPLAC_SPW = spw,
  * GAPLAC_PAIR_DEPTH = depth (0: auto), band extension pair_ext (0/1), GAPLAC_PAIR_M =
  * pair_m): every tile column gets every earlier panel column exactly once, in order, before

@@ -17,6 +17,9 @@
 //                                the product kernel against the first workspace and the scratch;
 //   gaplac_plan_check_sparse_grad_z - the same for gaplac_sparse_elbo_grad_z: the product's dZ
 //                                variant and the dZ launches, the partials as a third region;
+//   gaplac_plan_check_sparse_joint - the same for the sparse joint entries: the copy of the a rows,
+//                                the covariance launches against the second and third workspace,
+//                                the preloaded factorisation of order Ms, plain or with riding rows;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -153,6 +156,30 @@ int main() {
                        (long long)N, (long long)Mz);
                 ++checks;
             }
+    // the sparse joint entries: the sparse posterior's stages, the copy of the a rows, the covariance
+    // launches with the mirroring pass and the third factorisation (plain or with R riding rows);
+    // then each of the three workspaces one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t Mz : {1, 5, 127, 128, 129, 257, 1024, 4096})
+            for (int64_t Ms : {1, 3, 127, 128, 129, 1000, 10300})
+                for (int64_t R : {0, 1, 129})
+                    for (int64_t N : {1, 5, 127, 128, 129, 300, 1025, 2051, 16384, 70000}) {
+                        const int rc = gaplac_plan_check_sparse_joint(N, Mz, Ms, R, spw, 0, &a, &b, msg, sizeof msg);
+                        EXPECT(rc == 0 && a > 0 && b == 0,
+                               "plan_check_sparse_joint N=%lld Mz=%lld Ms=%lld R=%lld spw=%d: rc %d violations %lld %s",
+                               (long long)N, (long long)Mz, (long long)Ms, (long long)R, spw, rc, (long long)b, msg);
+                        ++checks;
+                    }
+    for (int short_ws : {1, 2, 3})
+        for (int64_t N : {1, 127, 300, 4096})
+            for (int64_t Ms : {1, 129, 1000})
+                for (int64_t R : {0, 3}) {
+                    const int rc = gaplac_plan_check_sparse_joint(N, 129, Ms, R, 4, short_ws, &a, &b, msg, sizeof msg);
+                    EXPECT(rc == 0 && b >= 1, "negative control (sparse joint, short_ws %d) N=%lld Ms=%lld R=%lld not reported",
+                           short_ws, (long long)N, (long long)Ms, (long long)R);
+                }
+    EXPECT(gaplac_plan_check_sparse_joint(10, 1, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG,
+           "sparse joint: Ms = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
