@@ -1487,7 +1487,10 @@ double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j, c
     double kd = 0.0, pr = 1.0;
     for (int t = 0; t < tp.T; ++t) {
         const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + j];
-        double k = 1.0;
+        double k = 1.0;  // CAT: kappa(d) = d > 0 ? 0 : 1 is 1 at any x, NaN included
+        // SQEXP / OU: exp(0) with u - u = 0, or NaN where the scaled coordinate u = x / l is not finite
+        // (u - u is NaN: the Gram's diagonal there)
+        if ((tp.kind[t] == GAPLAC_SQEXP || tp.kind[t] == GAPLAC_OU) && !std::isfinite(tp.p[t] * x)) k = NAN;
         if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
         if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
         pr *= !sel || sel->comp[t] == g ? k : 0.0;

@@ -199,7 +199,7 @@ __device__ __forceinline__ double gram_term(double xi, double xj, double p, int6
     } else if constexpr (KIND == GAPLAC_LINEAR) {
         return xi * xj + p;
     } else if constexpr (KIND == GAPLAC_CAT) {
-        return (xi == xj) ? 1.0 : 0.0;
+        return !(fabs(xi - xj) > 0.0) ? 1.0 : 0.0;  // kappa(d) = d > 0 ? 0 : 1: a NaN distance gives 1
     } else {  // GAPLAC_NOISE: index identity
         return (i == j) ? p : 0.0;
     }
@@ -1881,7 +1881,7 @@ __device__ __forceinline__ double term_k(int kind, double p, double xi, double x
         case GAPLAC_LINEAR:
             return xi * xj + p;
         case GAPLAC_CAT:
-            return (xi == xj) ? 1.0 : 0.0;
+            return !(fabs(xi - xj) > 0.0) ? 1.0 : 0.0;  // (gram_term's rule: a NaN distance gives 1)
         default:
             return diag ? p : 0.0;
     }

@@ -43,8 +43,11 @@ enum gaplac_kind {
                           k = exp(-|x_i - x_j|/l)                src/gp_parts.jl:37-43 */
     GAPLAC_LINEAR = 3, /* Linear(:x; c) -> LinearKernel(c): k = x_i*x_j + c, c >= 0
                                                                  src/gp_parts.jl:29-35 */
-    GAPLAC_CAT    = 4, /* Cat(:x)       -> CategoricalKernel: k = (x_i == x_j)
-                                                                 src/gp_parts.jl:11-13,45-47 */
+    GAPLAC_CAT    = 4, /* Cat(:x)       -> CategoricalKernel: k = |x_i - x_j| > 0 ? 0 : 1
+                          (the reference's kappa(d2) = d2 > 0 ? 0.0 : 1.0: equal categories 1,
+                          and a NaN category 1 with every point, itself included; a non-finite
+                          x under SQEXP / OU gives NaN where the difference is NaN, the prior
+                          variance k(x, x) included)     src/gp_parts.jl:11-13,45-47 */
     GAPLAC_NOISE  = 5  /* extension (absent in the reference):
                           k = param * delta_ij by index; col ignored */
 };

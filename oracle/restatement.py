@@ -88,10 +88,11 @@ def term_matrix(X: np.ndarray, kind: int, col: int, param: float, distances: str
             raise ValueError("LinearKernel: c >= 0 required")
         return np.outer(x, x) + param  # kappa(xᵀy) = xᵀy + c
     if kind == CAT:
-        if distances == "direct":
-            return (x[:, None] == x[None, :]).astype(np.float64)
-        d = _pair(x, "eu", distances)
-        return np.where(d > 0, 0.0, 1.0)
+        # CategoricalKernel: kappa(d) = d > 0 ? 0 : 1, in both distance forms. A NaN category has a
+        # NaN distance to everything, itself included, and NaN > 0 is false: covariance 1.
+        with np.errstate(invalid="ignore"):
+            d = np.abs(x[:, None] - x[None, :]) if distances == "direct" else _pair(x, "eu", distances)
+            return np.where(d > 0, 0.0, 1.0)
     raise ValueError(f"unknown term kind {kind}")
 
 
@@ -301,7 +302,8 @@ def cross_term_matrix(Xa: np.ndarray, Xb: np.ndarray, kind: int, col: int, param
     if kind == LINEAR:
         return np.outer(a, b) + param
     if kind == CAT:
-        return (a[:, None] == b[None, :]).astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            return np.where(np.abs(a[:, None] - b[None, :]) > 0, 0.0, 1.0)  # (term_matrix's rule)
     raise ValueError(f"unknown term kind {kind}")
 
 
