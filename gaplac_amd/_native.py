@@ -32,6 +32,12 @@ EXPORTED = (
     "gaplac_logpdf_grad_device",
     "gaplac_posterior_mean_var",
     "gaplac_posterior_components",
+    "gaplac_fit_create",
+    "gaplac_fit_destroy",
+    "gaplac_fit_info",
+    "gaplac_fit_alpha",
+    "gaplac_fit_mean",
+    "gaplac_fit_mean_var",
     "gaplac_rand",
     "gaplac_logpdf_multi",
     "gaplac_logpdf_multi_device",
@@ -56,6 +62,7 @@ EXPORTED = (
     "gaplac_plan_check",
     "gaplac_plan_check_schedule",
     "gaplac_plan_check_joint",
+    "gaplac_plan_check_fit",
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
     "gaplac_plan_check_sparse_grad_z",
@@ -171,6 +178,15 @@ def load() -> ctypes.CDLL:
     lib.gaplac_posterior_components.argtypes = common + [
         c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
     ]
+    # (the fitted posterior: create takes `common`, cap and the handle's address; the rest the handle)
+    lib.gaplac_fit_create.argtypes = common + [c_int64, POINTER(c_void_p)]
+    lib.gaplac_fit_destroy.argtypes = [c_void_p]
+    lib.gaplac_fit_info.argtypes = [c_void_p, POINTER(c_int64), POINTER(c_int64), _DP, _DP, _DP]
+    lib.gaplac_fit_alpha.argtypes = [c_void_p, c_void_p]
+    lib.gaplac_fit_mean.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p]
+    lib.gaplac_fit_mean_var.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.gaplac_plan_check_fit.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
+                                          POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_rand.argtypes = common + [c_void_p]
     # (the matrix forms take R, the matrix and its leading dimension where `common` ends in v)
     multi = common[:-1] + [c_int64, c_void_p, c_int64]

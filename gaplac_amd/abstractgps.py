@@ -109,7 +109,7 @@ def logpdf_and_gradient(fx: FiniteGP, y, ctx: backend.Context | None = None):
 class PosteriorGP:
     """AbstractGPs.posterior(fx, y): the GP conditioned on observations y at fx's inputs.
     Evaluation happens per query (mean_and_var at test inputs), one gaplac_posterior_mean_var
-    call each."""
+    call each; fit() returns the same posterior with the factorisation kept."""
 
     def __init__(self, fx: FiniteGP, y, ctx: backend.Context | None = None):
         y = np.asarray(y, dtype=np.float64)
@@ -148,10 +148,51 @@ class PosteriorGP:
     def var(self, x):
         return self.mean_and_var(x)[1]
 
+    def fit(self, cap: int = 1024):
+        """The posterior factored once and kept on the device (gaplac_fit_create), as AbstractGPs'
+        PosteriorGP keeps its Cholesky factor and α: a FittedPosteriorGP whose queries skip the
+        factorisation. cap: the test points solved at once (larger queries run in chunks)."""
+        _gate()
+        ctx = self.ctx or backend.default_context()
+        return FittedPosteriorGP(self, ctx.fit(self.prior.x, self.prior.terms, self.prior.noise, self.y, cap=cap))
+
     def __call__(self, x, noise=0.0):
         """AbstractGPs' fp(xs, σ²): the posterior at the rows of x, jointly, with observation
         variance noise there (a FiniteGP{<:PosteriorGP})."""
         return FinitePosteriorGP(self, x, noise)
+
+
+class FittedPosteriorGP:
+    """PosteriorGP.fit(): the same posterior behind a kept factorisation (backend.Fit). mean_and_var
+    and var solve the test rows against the kept factor (gaplac_fit_mean_var); mean alone is the
+    matrix-free K(xs, X) α (gaplac_fit_mean). Close it (or use it as a context manager) to free
+    the device memory early."""
+
+    def __init__(self, f: PosteriorGP, fit: "backend.Fit"):
+        self.f = f
+        self.prior = f.prior
+        self.y = f.y
+        self.handle = fit
+
+    def mean_and_var(self, x):
+        _gate()
+        return self.handle.mean_var(self.f._xs(x))
+
+    def mean(self, x):
+        _gate()
+        return self.handle.mean(self.f._xs(x))
+
+    def var(self, x):
+        return self.mean_and_var(x)[1]
+
+    def close(self):
+        self.handle.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class FinitePosteriorGP:

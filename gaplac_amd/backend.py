@@ -197,6 +197,24 @@ class Context:
         self._check(rc)
         return mean, var
 
+    def fit(self, X, terms, noise: float, y, cap: int = 1024) -> "Fit":
+        """The posterior given y, factored once and kept on the device (gaplac_fit_create): a Fit
+        whose queries skip the factorisation. cap: test points solved at once."""
+        Xc = _colmajor(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, D = Xc.shape
+        if y.ndim != 1 or y.shape[0] != N:
+            raise ArgumentError(f"length of y ({y.shape[0] if y.ndim else 0}) != N ({N})")
+        terms = list(terms)
+        ta = term_array(terms)
+        h = c_void_p()
+        rc = self.lib.gaplac_fit_create(
+            self.h, N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), ta, float(noise),
+            y.ctypes.data_as(c_void_p), int(cap), byref(h),
+        )
+        self._check(rc)
+        return Fit(self, h, D)
+
     def posterior_components(self, X, terms, noise: float, y, Xs, comp, G=None):
         """(mean[M, G], var[M, G]): the posterior of every component of k = sum_g k_g at the
         rows of Xs, all from one factorisation (gaplac_posterior_components). comp[t] is the
@@ -567,6 +585,89 @@ class Context:
 
     def reset_stats(self):
         self.lib.gaplac_reset_stats(self.h)
+
+
+class Fit:
+    """A fitted posterior (gaplac_fit): the factor, z and alpha = C^{-1} y kept on the device by
+    Context.fit. Queries cost the test rows' solve (mean_var) or a matrix-free product (mean), not
+    a factorisation. Free it with close() or a with-block; a Fit outlives neither its Context's
+    close() (every query then raises ArgumentError) nor its own."""
+
+    def __init__(self, ctx: Context, h: c_void_p, D: int):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.h = h
+        self.D = D
+        n, cap = c_int64(), c_int64()
+        lp, ld, q = c_double(), c_double(), c_double()
+        self.lib.gaplac_fit_info(h, byref(n), byref(cap), byref(lp), byref(ld), byref(q))
+        self.N, self.cap = n.value, cap.value
+        self.logpdf, self.logdet, self.quad = lp.value, ld.value, q.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.gaplac_fit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _handle(self):
+        if not getattr(self, "h", None):
+            raise ArgumentError("the fit is closed")
+        return self.h
+
+    def _check(self, rc: int):
+        if rc < 0 and not self.ctx.h:
+            raise ArgumentError(f"gaplac error {rc}: the fit's context is closed")
+        self.ctx._check(rc)
+
+    def _xs(self, Xs):
+        Xsc = _colmajor(Xs)
+        if Xsc.shape[1] != self.D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {self.D}")
+        return Xsc
+
+    def alpha(self) -> np.ndarray:
+        """alpha = C^{-1} y (gaplac_fit_alpha)."""
+        h = self._handle()
+        out = np.empty(self.N, dtype=np.float64)
+        buf = out if self.N else np.empty(1)  # (an empty result still passes a valid pointer)
+        self._check(self.lib.gaplac_fit_alpha(h, buf.ctypes.data_as(c_void_p)))
+        return out
+
+    def mean(self, Xs) -> np.ndarray:
+        """Posterior mean at the rows of Xs, matrix-free (gaplac_fit_mean)."""
+        h = self._handle()
+        Xsc = self._xs(Xs)
+        M = Xsc.shape[0]
+        mean = np.empty(M, dtype=np.float64)
+        mb = mean if M else np.empty(1)
+        self._check(self.lib.gaplac_fit_mean(h, M, Xsc.ctypes.data_as(c_void_p), max(M, 1), mb.ctypes.data_as(c_void_p)))
+        return mean
+
+    def mean_var(self, Xs):
+        """(mean, var) at the rows of Xs (gaplac_fit_mean_var): the arithmetic of
+        Context.posterior_mean_var without its factorisation."""
+        h = self._handle()
+        Xsc = self._xs(Xs)
+        M = Xsc.shape[0]
+        mean = np.empty(M, dtype=np.float64)
+        var = np.empty(M, dtype=np.float64)
+        mb = mean if M else np.empty(1)
+        vb = var if M else np.empty(1)
+        self._check(self.lib.gaplac_fit_mean_var(h, M, Xsc.ctypes.data_as(c_void_p), max(M, 1),
+                                                 mb.ctypes.data_as(c_void_p), vb.ctypes.data_as(c_void_p)))
+        return mean, var
 
 
 _default_ctx: Context | None = None

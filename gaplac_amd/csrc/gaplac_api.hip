@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -171,6 +172,9 @@ struct gaplac_ctx {
     // Batched select: models in flight on independent lanes (child contexts with their
     // own workspace and streams; they read the parent's uploaded X and v).
     std::vector<gaplac_ctx*> lanes;
+    // Fitted posteriors created on this context (gaplac_fit_create): each owns
+    // its device buffer; gaplac_ctx_destroy frees the buffers and orphans the handles
+    std::vector<struct gaplac_fit*> fits;
     int batch_lanes = 2;           // GAPLAC_BATCH_LANES (measured at N=8192: 1 lane 138, 2 lanes 191, 3-6 lanes 161-187 evals/s)
     int tail_share = 1;            // lanes sharing the GPU (gaplac_logpdf_batch): tail grid = CUs / share
     int batch_w = 32;              // GAPLAC_BATCH_W: models per tail launch when the whole matrix is in the tail
@@ -2708,6 +2712,225 @@ static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& 
     return rc;
 }
 
+// ---------------------------------------------------------------------------------
+// Fitted posterior: one factorisation kept, queried many times.
+// ---------------------------------------------------------------------------------
+
+// Where everything a fit keeps lies in its one device buffer (offsets in doubles). L comes first
+// (the launchers' footprints are relative to it) and alpha last: the back-substitution's first
+// launch writes the buffer's last element, so a buffer one element short is always reported.
+struct FitDims {
+    int64_t Np, ldl, nk, nkm, qc, Dm;
+    int nt;
+    int64_t L, dinv, X, Xs, part, mean, var, tp, alpha, elems;
+};
+// test points per launch of the matrix-free mean (it needs no riding rows, so cap does not bind it)
+constexpr int64_t FIT_MEAN_CHUNK = 8192;
+
+static FitDims fit_dims(int64_t N, int32_t D, int64_t cap) {
+    FitDims d{};
+    d.Np = round_up(N + 1, NB);
+    d.nt = (int)(d.Np / NB);
+    const int64_t ct = (cap + NB - 1) / NB;
+    d.ldl = d.Np + NB * ct;
+    d.nk = (N + 511) / 512;
+    d.nkm = (N + 255) / 256;
+    d.qc = std::max(cap, FIT_MEAN_CHUNK);
+    d.Dm = D > 0 ? D : 1;
+    d.L = 0;
+    d.dinv = d.L + d.ldl * d.Np;
+    d.X = d.dinv + (int64_t)d.nt * DINV_PER_BLOCK;
+    d.Xs = d.X + N * d.Dm;
+    d.part = d.Xs + d.qc * d.Dm;
+    d.mean = d.part + std::max(2 * d.nk * cap, d.nkm * d.qc);
+    d.var = d.mean + d.qc;
+    d.tp = d.var + d.qc;
+    d.alpha = d.tp + (int64_t)((sizeof(TermPack) + 7) / 8);
+    d.elems = d.alpha + N;
+    return d;
+}
+
+struct gaplac_fit {
+    gaplac_ctx* ctx = nullptr;  // nullptr once the context has been destroyed
+    int device = 0;
+    int64_t N = 0, cap = 0;
+    int32_t D = 0;
+    TermPack tp{};  // host copy (noise inside)
+    double logpdf = NAN, logdet = NAN, quad = NAN;
+    FitDims d{};
+    double* buf = nullptr;
+};
+
+// The create-time launches after the evaluation: the factor's lower tiles out of the context's
+// workspace A (ld lda), z out of the factor's row N into alpha, and the back-substitution.
+static void fit_create_launches(hipStream_t s, const FitDims& d, int64_t N, const double* A, int64_t lda,
+                                double* buf) {
+    launch_fit_copy(s, A, lda, d.nt, buf + d.L, d.ldl);
+    launch_copy_z(s, buf + d.L, d.ldl, N, buf + d.alpha);
+    launch_fit_backsub(s, buf + d.L, d.ldl, N, buf + d.alpha);
+}
+
+// One chunk of m <= cap test points (their inputs at d.Xs, ld m): K(xs, X) into the reserved
+// rows, the rows' solve against the factor, mean and variance into d.mean / d.var.
+static void fit_query_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, int W, double* buf) {
+    const int mt = (int)((m + NB - 1) / NB);
+    const TermPack* dtp = reinterpret_cast<const TermPack*>(buf + d.tp);
+    launch_cross_gram(s, buf + d.L, d.ldl, d.Np, d.nt, N, m, mt, buf + d.X, N, buf + d.Xs, m, dtp);
+    launch_fit_rows_solve(s, buf + d.L, d.ldl, d.nt, mt, W, buf + d.dinv);
+    launch_posterior(s, buf + d.L, d.ldl, d.Np, N, m, buf + d.Xs, m, dtp, buf + d.part, buf + d.mean, buf + d.var);
+}
+
+static void fit_mean_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, double* buf) {
+    launch_fit_mean(s, N, m, buf + d.X, N, buf + d.alpha, buf + d.Xs, m,
+                    reinterpret_cast<const TermPack*>(buf + d.tp), buf + d.part, buf + d.mean);
+}
+
+static void fit_unregister(gaplac_fit* f) {
+    if (!f->ctx) return;
+    auto& v = f->ctx->fits;
+    v.erase(std::remove(v.begin(), v.end(), f), v.end());
+    f->ctx = nullptr;
+}
+
+static int fit_create_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                           const gaplac_term* terms, double noise, const double* y, int64_t cap, gaplac_fit** out) {
+    if (!out) return ctx ? set_err(ctx, GAPLAC_E_ARG, "out is NULL") : GAPLAC_E_ARG;
+    *out = nullptr;
+    int rc = check_common(ctx, N, D, X, ldx, noise, y);
+    if (rc) return rc;
+    if (cap < 1) return set_err(ctx, GAPLAC_E_ARG, "cap = %lld < 1", (long long)cap);
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    tp.noise = noise;
+    std::unique_ptr<gaplac_fit> f(new gaplac_fit());
+    f->device = ctx->device;
+    f->N = N;
+    f->cap = cap;
+    f->D = D;
+    f->tp = tp;
+    if (N == 0) {  // the empty FiniteGP: its logpdf, and the prior at every query
+        f->logpdf = -0.0;
+        f->logdet = f->quad = 0.0;
+    } else {
+        if ((cap + NB - 1) / NB > 65535)
+            return set_err(ctx, GAPLAC_E_OOM, "cap = %lld: more than 65535 tile rows", (long long)cap);
+        HIPCK(ctx, hipSetDevice(ctx->device));
+        if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
+        EvalResult r;
+        if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}, &r))) return rc;
+        if ((rc = finish(r, &f->logpdf, &f->logdet, &f->quad)))
+            return set_err(ctx, rc, "K(X) + noise I (order %lld) is not positive definite: its Cholesky factorisation "
+                                    "failed at leading minor %d; no fit",
+                           (long long)N, rc);
+        f->d = fit_dims(N, D, cap);
+        const FitDims& d = f->d;
+        if (hipMalloc(reinterpret_cast<void**>(&f->buf), (size_t)d.elems * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            f->buf = nullptr;
+            return set_err(ctx, GAPLAC_E_OOM, "hipMalloc of the fit's %lld bytes failed", (long long)d.elems * 8);
+        }
+        struct Drop {  // the buffer goes with a failed create
+            gaplac_fit* f;
+            bool keep = false;
+            ~Drop() {
+                if (!keep && f->buf) (void)hipFree(f->buf);
+            }
+        } drop{f.get()};
+        hipStream_t s = ctx->s_main;
+        rc = guarded_on(ctx, f->buf, (size_t)d.elems, ctx->A, ctx->A_elems,
+                        [&] { fit_create_launches(s, d, N, ctx->A, d.Np, f->buf); });
+        if (rc) {
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+        HIPCK(ctx, hipMemcpyAsync(f->buf + d.dinv, ctx->Dinv, (size_t)d.nt * DINV_PER_BLOCK * 8, hipMemcpyDeviceToDevice, s));
+        if (D > 0)
+            HIPCK(ctx, hipMemcpyAsync(f->buf + d.X, ctx->dX, (size_t)N * D * 8, hipMemcpyDeviceToDevice, s));
+        HIPCK(ctx, hipMemcpyAsync(f->buf + d.tp, ctx->dtp, sizeof(TermPack), hipMemcpyDeviceToDevice, s));
+        HIPCK(ctx, hipStreamSynchronize(s));
+        drop.keep = true;
+    }
+    f->ctx = ctx;
+    ctx->fits.push_back(f.get());
+    *out = f.release();
+    return 0;
+}
+
+// Argument checks the queries share; 1: nothing to do (M = 0), 0: go on.
+static int fit_query_check(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs) {
+    if (!f || !f->ctx) return GAPLAC_E_ARG;
+    gaplac_ctx* ctx = f->ctx;
+    if (M < 0) return set_err(ctx, GAPLAC_E_ARG, "M = %lld < 0", (long long)M);
+    if (M > 0 && f->D > 0 && (!Xs || ldxs < M))
+        return set_err(ctx, GAPLAC_E_ARG, "Xs NULL or ldxs %lld < M %lld", (long long)ldxs, (long long)M);
+    return M == 0 ? 1 : 0;
+}
+
+// rows [r0, r0 + m) of the host block Xs into the fit's test inputs (ld m)
+static int fit_upload_xs(gaplac_fit* f, int64_t r0, int64_t m, const double* Xs, int64_t ldxs) {
+    if (f->D > 0)
+        HIPCK(f->ctx, hipMemcpy2DAsync(f->buf + f->d.Xs, (size_t)m * 8, Xs + r0, (size_t)ldxs * 8, (size_t)m * 8,
+                                       (size_t)f->D, hipMemcpyHostToDevice, f->ctx->s_main));
+    return 0;
+}
+
+static int fit_mean_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean) {
+    for (int64_t j = 0; out_mean && j < M; ++j) out_mean[j] = NAN;
+    int rc = fit_query_check(f, M, Xs, ldxs);
+    if (rc) return rc > 0 ? 0 : rc;
+    gaplac_ctx* ctx = f->ctx;
+    if (!out_mean) return set_err(ctx, GAPLAC_E_ARG, "out_mean is NULL");
+    if (f->N == 0) {
+        for (int64_t j = 0; j < M; ++j) out_mean[j] = 0.0;
+        return 0;
+    }
+    HIPCK(ctx, hipSetDevice(f->device));
+    const FitDims& d = f->d;
+    hipStream_t s = ctx->s_main;
+    for (int64_t r0 = 0; r0 < M; r0 += d.qc) {
+        const int64_t m = std::min(d.qc, M - r0);
+        if ((rc = fit_upload_xs(f, r0, m, Xs, ldxs))) return rc;
+        if ((rc = guarded_on(ctx, f->buf, (size_t)d.elems, nullptr, 0, [&] { fit_mean_launches(s, d, f->N, m, f->buf); })))
+            return rc;
+        HIPCK(ctx, hipMemcpyAsync(out_mean + r0, f->buf + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        HIPCK(ctx, hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
+static int fit_mean_var_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
+                             double* out_var) {
+    if (!out_var) return fit_mean_impl(f, M, Xs, ldxs, out_mean);
+    for (int64_t j = 0; j < M; ++j) {
+        if (out_mean) out_mean[j] = NAN;
+        out_var[j] = NAN;
+    }
+    int rc = fit_query_check(f, M, Xs, ldxs);
+    if (rc) return rc > 0 ? 0 : rc;
+    gaplac_ctx* ctx = f->ctx;
+    if (f->N == 0) {  // the prior
+        for (int64_t j = 0; j < M; ++j) {
+            if (out_mean) out_mean[j] = 0.0;
+            out_var[j] = host_kdiag(f->tp, Xs, ldxs, j);
+        }
+        return 0;
+    }
+    HIPCK(ctx, hipSetDevice(f->device));
+    const FitDims& d = f->d;
+    hipStream_t s = ctx->s_main;
+    for (int64_t r0 = 0; r0 < M; r0 += f->cap) {
+        const int64_t m = std::min(f->cap, M - r0);
+        if ((rc = fit_upload_xs(f, r0, m, Xs, ldxs))) return rc;
+        if ((rc = guarded_on(ctx, f->buf, (size_t)d.elems, nullptr, 0,
+                             [&] { fit_query_launches(s, d, f->N, m, ctx->spw, f->buf); })))
+            return rc;
+        if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean + r0, f->buf + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        HIPCK(ctx, hipMemcpyAsync(out_var + r0, f->buf + d.var, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        HIPCK(ctx, hipStreamSynchronize(s));
+    }
+    return 0;
+}
+
 extern "C" {
 
 int gaplac_abi_version(void) { return GAPLAC_ABI_VERSION; }
@@ -2781,6 +3004,12 @@ int gaplac_ctx_destroy(gaplac_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)sync_streams(ctx);
     for (gaplac_ctx* c : ctx->lanes) gaplac_ctx_destroy(c);
+    for (gaplac_fit* f : ctx->fits) {  // the handles stay valid for gaplac_fit_destroy; every other call fails
+        if (f->buf) (void)hipFree(f->buf);
+        f->buf = nullptr;
+        f->ctx = nullptr;
+    }
+    ctx->fits.clear();
     if (ctx->borrowed_inputs) {
         ctx->dX = nullptr;
         ctx->dv = nullptr;
@@ -3243,6 +3472,83 @@ int gaplac_sparse_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const 
                                    double* out_logpdf, double* out_logdet, double* out_quad) {
     return sparse_posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs,
                                         noise_s, R, Ys, ldys, out_logpdf, out_logdet, out_quad);
+}
+
+int gaplac_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                      const gaplac_term* terms, double noise, const double* y, int64_t cap, gaplac_fit** out) {
+    return fit_create_impl(ctx, N, D, X, ldx, T, terms, noise, y, cap, out);
+}
+
+int gaplac_fit_destroy(gaplac_fit* fit) {
+    if (!fit) return 0;
+    if (fit->ctx) {
+        (void)hipSetDevice(fit->device);
+        (void)hipStreamSynchronize(fit->ctx->s_main);
+        fit_unregister(fit);
+    }
+    if (fit->buf) (void)hipFree(fit->buf);
+    delete fit;
+    return 0;
+}
+
+int gaplac_fit_info(const gaplac_fit* fit, int64_t* out_N, int64_t* out_cap, double* out_logpdf, double* out_logdet,
+                    double* out_quad) {
+    if (!fit) return GAPLAC_E_ARG;
+    if (out_N) *out_N = fit->N;
+    if (out_cap) *out_cap = fit->cap;
+    if (out_logpdf) *out_logpdf = fit->logpdf;
+    if (out_logdet) *out_logdet = fit->logdet;
+    if (out_quad) *out_quad = fit->quad;
+    return 0;
+}
+
+int gaplac_fit_alpha(gaplac_fit* fit, double* out_alpha) {
+    if (!fit) return GAPLAC_E_ARG;
+    for (int64_t i = 0; out_alpha && i < fit->N; ++i) out_alpha[i] = NAN;
+    if (!fit->ctx) return GAPLAC_E_ARG;
+    if (fit->N == 0) return 0;
+    if (!out_alpha) return set_err(fit->ctx, GAPLAC_E_ARG, "out_alpha is NULL");
+    HIPCK(fit->ctx, hipSetDevice(fit->device));
+    HIPCK(fit->ctx, hipMemcpy(out_alpha, fit->buf + fit->d.alpha, (size_t)fit->N * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int gaplac_fit_mean(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean) {
+    return fit_mean_impl(fit, M, Xs, ldxs, out_mean);
+}
+
+int gaplac_fit_mean_var(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
+                        double* out_var) {
+    return fit_mean_var_impl(fit, M, Xs, ldxs, out_mean, out_var);
+}
+
+// Host-only walk of a fit (no device needed): the create-time copy, z and the back-substitution
+// against the fit's buffer (the evaluation before them is gaplac_plan_check's mode 0), then one
+// mean-and-variance query of M points in chunks of cap and one matrix-free mean query, every
+// launch through the functions the entries call. short_ws 1: the buffer one element short.
+int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                          int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || cap < 1 || M < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 1) return GAPLAC_E_ARG;
+    if ((cap + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
+    const FitDims d = fit_dims(N, 1, cap);
+    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    LaunchGuard g;
+    g.base = fb;
+    g.elems = d.elems - (short_ws == 1 ? 1 : 0);
+    g.base2 = fa;
+    g.elems2 = d.Np * d.Np;
+    g.dry = true;
+    {
+        GuardScope scope(&g);
+        fit_create_launches(nullptr, d, N, fa, d.Np, fb);
+        for (int64_t r0 = 0; r0 < M; r0 += cap) fit_query_launches(nullptr, d, N, std::min(cap, M - r0), spw, fb);
+        for (int64_t r0 = 0; r0 < M; r0 += d.qc) fit_mean_launches(nullptr, d, N, std::min(d.qc, M - r0), fb);
+    }
+    if (out_launches) *out_launches = g.launches;
+    if (out_violations) *out_violations = g.violations;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
+    return 0;
 }
 
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {

@@ -330,6 +330,22 @@ void launch_cross_gram(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt
 void launch_posterior(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, int64_t M,
                       const double* Xs, int64_t ldxs, const TermPack* dtp, double* partial, double* mean,
                       double* var, const CompSel* sel = nullptr);
+// ---- fitted posterior ----
+// The lower 128x128 tiles of the nt x nt tile factor in A (ld lda; the guard's second allocation)
+// into L (ld ldl; its first).
+void launch_fit_copy(hipStream_t s, const double* A, int64_t lda, int nt, double* L, int64_t ldl);
+// a (N values, holding z = L^{-1} y; the same guarded allocation as L) = L^{-T} a over the order-N
+// factor in L: per tile column, last to first, the diagonal tile's substitution in one workgroup,
+// then its contribution to every earlier entry (one launch each; bitwise repeatable).
+void launch_fit_backsub(hipStream_t s, const double* L, int64_t ldl, int64_t N, double* a);
+// The mt tile rows below the finished factor in L (tile rows nt .. nt + mt - 1) solved against it:
+// rows <- rows L^{-T}, super-panel by super-panel of W tile columns, the riding rows' launches of
+// the factorisation's schedule (extra_rows_chain / extra_rows_update) on one stream.
+void launch_fit_rows_solve(hipStream_t s, double* L, int64_t ldl, int nt, int mt, int W, const double* Dinv);
+// mean_j = sum_n k(xs_j, x_n) alpha_n, j < M, matrix-free (part: ceil(N / 256) * M doubles; part
+// and mean in the guarded allocation).
+void launch_fit_mean(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* alpha,
+                     const double* Xs, int64_t ldxs, const TermPack* dtp, double* part, double* mean);
 // ---- rand(FiniteGP): out = L z over the factor's lower triangle (partial: ceil(N/512) * N) ----
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,
                      double* out);

@@ -5123,4 +5123,241 @@ void launch_init_result_ctl(hipStream_t s, EvalResult* res, TailCtl* ctl, const 
                                                           (int)(sizeof(TailCtl) / sizeof(unsigned)), tp, dtp);
 }
 
+// (The fitted posterior's kernels and launchers stand last in this file: the code object keeps the
+// layout of every kernel before them.)
+// ---------------------------------------------------------------------------------
+// Fitted posterior: the finished factor kept in a buffer of its own (leading
+// dimension ldl = Np + 128 ceil(cap / 128): room for cap riding rows below it), alpha = L^{-T} z
+// by back-substitution, and the matrix-free mean K(xs, X) alpha.
+// ---------------------------------------------------------------------------------
+
+// Lower tile (bi, bj) of the factor from the context's workspace (ld lda) into the fit's (ld ldl).
+__global__ __launch_bounds__(256) void fit_copy_tiles_kernel(const double* __restrict__ A, int64_t lda,
+                                                             double* __restrict__ L, int64_t ldl) {
+    const int bi = (int)blockIdx.x, bj = (int)blockIdx.y;
+    if (bi < bj) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const double* src = A + (int64_t)bj * NB * lda + (int64_t)bi * NB + 2 * lane;
+    double* dst = L + (int64_t)bj * NB * ldl + (int64_t)bi * NB + 2 * lane;
+    for (int c = w; c < NB; c += 4)
+        *reinterpret_cast<double2*>(dst + (int64_t)c * ldl) = *reinterpret_cast<const double2*>(src + (int64_t)c * lda);
+}
+
+// Back-substitution, tile column c (rows / columns c NB .. c NB + nc - 1 of the order-N factor):
+// a holds the right-hand side of L_cc^T x = a in those entries (z minus the later tile columns'
+// contributions) and gets x. The diagonal tile's lower triangle is staged packed in LDS (column j
+// at FIT_OFF(j), rows j .. 127); one wave then solves right-looking from the last row up, two
+// entries per lane: x_i = a_i / L_ii is broadcast (v_readlane) and every earlier entry j < i
+// takes a_j -= L_ij x_i. No reduction: the order of every sum is the row order.
+#define FIT_OFF(j) ((j) * NB - (j) * ((j) - 1) / 2)
+constexpr int FIT_PACKED = NB * (NB + 1) / 2;
+__global__ __launch_bounds__(256) void fit_backsub_diag_kernel(const double* __restrict__ L, int64_t ldl, int c,
+                                                               int nc, double* __restrict__ a) {
+    __shared__ double Ls[FIT_PACKED];
+    __shared__ double rd[NB];
+    const int tid = threadIdx.x;
+    const double* Lcc = L + (int64_t)c * NB * ldl + (int64_t)c * NB;
+    // the whole tile is read (all of it lies inside the factor's storage; what is above the
+    // diagonal or below row nc is never used), all 64 loads of a thread in flight at once: the
+    // launch is one of a dependent chain, so the staging's latency counts, not its bandwidth
+    {
+        double v[64];
+#pragma unroll
+        for (int u = 0; u < 64; ++u) {
+            const int idx = tid + 256 * u;
+            v[u] = Lcc[(int64_t)(idx >> 7) * ldl + (idx & (NB - 1))];
+        }
+#pragma unroll
+        for (int u = 0; u < 64; ++u) {
+            const int idx = tid + 256 * u;
+            const int j = idx >> 7, i = idx & (NB - 1);
+            if (i >= j) Ls[FIT_OFF(j) + i - j] = v[u];
+        }
+    }
+    if (tid < NB) rd[tid] = tid < nc ? 1.0 / Lcc[(int64_t)tid * ldl + tid] : 0.0;
+    __syncthreads();
+    if (tid >= 64) return;
+    const int lane = tid;
+    double* ac = a + (int64_t)c * NB;
+    double b0 = lane < nc ? ac[lane] : 0.0, b1 = lane + 64 < nc ? ac[lane + 64] : 0.0;
+    // L[i, lane] and L[i, lane + 64]; for a column beyond row i the index falls into the column
+    // before it (still inside Ls) and the value is not used
+    auto l0 = [&](int i) { return Ls[FIT_OFF(lane) + i - lane]; };
+    auto l1 = [&](int i) { return Ls[FIT_OFF(lane + 64) + i - lane - 64]; };
+    // Fixed trip counts (a step i >= nc of the last, partial tile is exact nothing: its entry and
+    // rd are 0 and its factors are read as 0), unrolled by 8: the LDS reads do not depend on the
+    // recurrence, so a group's reads are issued ahead of its chain, which is per step v_readlane,
+    // a multiply and the fused update.
+#pragma unroll 8
+    for (int i = NB - 1; i >= 64; --i) {
+        const bool on = i < nc;
+        const double f0 = on ? l0(i) : 0.0, f1 = on ? l1(i) : 0.0;
+        const double x = readlane_d(b1, i - 64) * rd[i];
+        b0 = fma(-f0, x, b0);
+        b1 = lane + 64 < i ? fma(-f1, x, b1) : lane + 64 == i ? x : b1;
+    }
+#pragma unroll 8
+    for (int i = 63; i >= 0; --i) {
+        const double f0 = i < nc ? l0(i) : 0.0;
+        const double x = readlane_d(b0, i) * rd[i];
+        b0 = lane < i ? fma(-f0, x, b0) : lane == i ? x : b0;
+    }
+    if (lane < nc) ac[lane] = b0;
+    if (lane + 64 < nc) ac[lane + 64] = b1;
+}
+
+// The solved tile column c applied to every earlier entry: a_j -= sum_r L[c NB + r, j] a[c NB + r],
+// r < nc, j < c NB. One wave per column j at a time (FIT_UPD_COLS columns per workgroup), two rows
+// per lane (a 1 KiB contiguous read of column j), summed by a fixed butterfly; every a_j is
+// written by one lane only, so the tile columns' contributions arrive in the launch order, last
+// to first.
+constexpr int FIT_UPD_COLS = 32;
+__global__ __launch_bounds__(256) void fit_backsub_update_kernel(const double* __restrict__ L, int64_t ldl, int c,
+                                                                 int nc, double* __restrict__ a) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r0 = 2 * lane;
+    const double x0 = r0 < nc ? a[(int64_t)c * NB + r0] : 0.0, x1 = r0 + 1 < nc ? a[(int64_t)c * NB + r0 + 1] : 0.0;
+    const int64_t jend = (int64_t)c * NB;
+    const int64_t j0 = (int64_t)blockIdx.x * FIT_UPD_COLS + w * (FIT_UPD_COLS / 4);
+    double s[FIT_UPD_COLS / 4];
+#pragma unroll
+    for (int q = 0; q < FIT_UPD_COLS / 4; ++q) {
+        const int64_t j = j0 + q;
+        double2 l = make_double2(0.0, 0.0);
+        if (j < jend) l = *reinterpret_cast<const double2*>(L + j * ldl + (int64_t)c * NB + r0);
+        s[q] = (r0 < nc ? l.x * x0 : 0.0) + (r0 + 1 < nc ? l.y * x1 : 0.0);
+    }
+#pragma unroll
+    for (int q = 0; q < FIT_UPD_COLS / 4; ++q) {
+        const double t = wave_sum(s[q]);
+        if (lane == 0 && j0 + q < jend) a[j0 + q] -= t;
+    }
+}
+
+// Matrix-free posterior mean, partial sums: workgroup (x, y) = test points 64 x .. 64 x + 63 (one
+// per lane, the same in all four waves) against the training points of chunk y (FIT_MEAN_NC of
+// them, their coordinates and alpha staged in LDS and read as broadcasts), a quarter of the chunk
+// per wave in ascending order; the four quarters are then added in ascending order. The kernel is
+// cross_gram_kernel's (term_k per term, product groups, an index-noise term 0 across point sets)
+// with the product by alpha in the place of the store, so nothing of size M x N exists. A test
+// point's sum never depends on its lane, on M or on the other points.
+constexpr int FIT_MEAN_NC = 256;
+__global__ __launch_bounds__(256) void fit_mean_partial_kernel(int64_t N, int64_t M, const double* __restrict__ X,
+                                                               int64_t ldx, const double* __restrict__ alpha,
+                                                               const double* __restrict__ Xs, int64_t ldxs,
+                                                               const TermPack* __restrict__ tpp,
+                                                               double* __restrict__ part) {
+    __shared__ double xcol[GAPLAC_MAX_TERMS][FIT_MEAN_NC];
+    __shared__ double as[FIT_MEAN_NC];
+    __shared__ double red[4][64];
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t n0 = (int64_t)blockIdx.y * FIT_MEAN_NC;
+    for (int idx = tid; idx < T * FIT_MEAN_NC; idx += 256) {
+        const int t = idx / FIT_MEAN_NC, cc = idx % FIT_MEAN_NC;
+        xcol[t][cc] = (n0 + cc < N && tp.kind[t] != GAPLAC_NOISE) ? X[(int64_t)tp.col[t] * ldx + n0 + cc] : 0.0;
+    }
+    as[tid] = n0 + tid < N ? alpha[n0 + tid] : 0.0;
+    const int64_t j = (int64_t)blockIdx.x * 64 + lane;
+    double xa[GAPLAC_MAX_TERMS];
+#pragma unroll
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+        xa[t] = 0.0;
+        if (t < T && tp.kind[t] != GAPLAC_NOISE && j < M) xa[t] = Xs[(int64_t)tp.col[t] * ldxs + j];
+    }
+    __syncthreads();
+    const int kn = (int)((N - n0) < FIT_MEAN_NC ? (N - n0) : FIT_MEAN_NC);
+    const int ce = (64 * w + 64) < kn ? (64 * w + 64) : kn;
+    double s = 0.0;
+    for (int cc = 64 * w; cc < ce; ++cc) {
+        double tot = 0.0, pr = 1.0;
+#pragma unroll
+        for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+            if (t < T) {
+                const int kind = tp.kind[t];
+                pr *= kind == GAPLAC_NOISE ? 0.0 : term_k(kind, tp.p[t], xa[t], xcol[t][cc], false);
+                if (tp.last_in_group[t]) {
+                    tot += pr;
+                    pr = 1.0;
+                }
+            }
+        }
+        s = fma(tot, as[cc], s);
+    }
+    red[w][lane] = s;
+    __syncthreads();
+    if (w == 0 && j < M) part[(int64_t)blockIdx.y * M + j] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+// mean_j = the chunks' partial sums in ascending order.
+__global__ __launch_bounds__(256) void fit_mean_finish_kernel(const double* __restrict__ part, int64_t M, int nk,
+                                                              double* __restrict__ mean) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= M) return;
+    double m = 0.0;
+    for (int y = 0; y < nk; ++y) m += part[(int64_t)y * M + j];
+    mean[j] = m;
+}
+
+void launch_fit_copy(hipStream_t s, const double* A, int64_t lda, int nt, double* L, int64_t ldl) {
+    if (nt <= 0) return;
+    bool ok = guard_launch("fit_copy_tiles_kernel", L, 0, tiles_end(ldl, nt - 1, nt - 1));
+    ok = guard_launch("fit_copy_tiles_kernel (source)", A, 0, tiles_end(lda, nt - 1, nt - 1), 1) && ok;
+    if (!ok) return;
+    fit_copy_tiles_kernel<<<dim3((unsigned)nt, (unsigned)nt), dim3(256), 0, s>>>(A, lda, L, ldl);
+}
+
+void launch_fit_backsub(hipStream_t s, const double* L, int64_t ldl, int64_t N, double* a) {
+    const int m = (int)((N + NB - 1) / NB);
+    for (int c = m - 1; c >= 0; --c) {
+        const int nc = (int)std::min<int64_t>(NB, N - (int64_t)c * NB);
+        bool ok = guard_launch("fit_backsub_diag_kernel", L, 0, tiles_end(ldl, c, c));
+        ok = guard_launch("fit_backsub_diag_kernel (alpha)", a, (int64_t)c * NB, (int64_t)c * NB + nc) && ok;
+        if (ok) fit_backsub_diag_kernel<<<dim3(1), dim3(256), 0, s>>>(L, ldl, c, nc, a);
+        if (c == 0) break;
+        ok = guard_launch("fit_backsub_update_kernel", L, 0, tiles_end(ldl, c, c - 1));
+        ok = guard_launch("fit_backsub_update_kernel (alpha)", a, 0, (int64_t)c * NB + nc) && ok;
+        const int64_t blocks = ((int64_t)c * NB + FIT_UPD_COLS - 1) / FIT_UPD_COLS;
+        if (ok) fit_backsub_update_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(L, ldl, c, nc, a);
+    }
+}
+
+void launch_fit_rows_solve(hipStream_t s, double* L, int64_t ldl, int nt, int mt, int W, const double* Dinv) {
+    if (mt <= 0) return;
+    for (int c0 = 0; c0 < nt; c0 += W) {
+        const int c1 = std::min(c0 + W, nt);
+        for (int c = c0; c < c1; ++c) {
+            double* Lcol = L + (int64_t)c * NB * ldl;
+            if (c > c0) {  // column c - 1 of the rows applied to the super-panel's columns from c on
+                BulkArgs ba{L, ldl, Panel{Lcol - NB * ldl, ldl, 0}, nullptr, mt * (c1 - c), NB, nt, c, ColMap{1, 0, W}};
+                ba.rect_rows = mt;
+                ba.tile_min = 128;
+                launch_bulk(s, ba, nullptr);
+            }
+            launch_trsm_rows(s, Lcol, ldl, c, nt, mt, Dinv + (size_t)c * DINV_PER_BLOCK, nullptr);
+        }
+        if (c1 < nt) {  // the super-panel's columns of the rows applied to every later column
+            BulkArgs ba{L, ldl, Panel{L + (int64_t)c0 * NB * ldl, ldl, 0}, nullptr, mt * (nt - c1), (c1 - c0) * NB, nt, c1,
+                        ColMap{1, 0, W}};
+            ba.rect_rows = mt;
+            ba.tile_min = 128;
+            launch_bulk(s, ba, nullptr);
+        }
+    }
+}
+
+void launch_fit_mean(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* alpha,
+                     const double* Xs, int64_t ldxs, const TermPack* dtp, double* part, double* mean) {
+    if (M <= 0 || N <= 0) return;
+    const int64_t nk = (N + FIT_MEAN_NC - 1) / FIT_MEAN_NC, bx = (M + 63) / 64;
+    // (grid limits: the caller chunks M; N / 256 > 65535 would need a factor of over a petabyte)
+    bool ok = guard_launch("fit_mean_partial_kernel", part, 0, nk * M);
+    ok = guard_launch("fit_mean_finish_kernel", mean, 0, M) && ok;
+    if (!ok) return;
+    fit_mean_partial_kernel<<<dim3((unsigned)bx, (unsigned)nk), dim3(256), 0, s>>>(N, M, X, ldx, alpha, Xs, ldxs, dtp,
+                                                                                 part);
+    fit_mean_finish_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s>>>(part, M, (int)nk, mean);
+}
+
 }  // namespace gaplac

@@ -188,6 +188,50 @@ int gaplac_posterior_components(gaplac_ctx* ctx, int64_t N, int32_t D, const dou
                                 int32_t G, const int32_t* comp,
                                 double* out_mean, int64_t ldm, double* out_var, int64_t ldv);
 
+/* Fitted posterior: the factorisation done once and kept, then queried at any number of test
+ * sets (what AbstractGPs' PosteriorGP holds: the Cholesky factor and alpha = C^{-1} y).
+ * The create entry runs the evaluation of the plain logpdf entry (its logpdf, logdet and quad
+ * are bitwise that entry's for the same arguments) and moves the factor's lower tiles, the
+ * diagonal blocks' inverses, z = L^{-1} y, X, the terms and noise into device memory the fit
+ * owns, with room for cap test rows below the factor; it then computes alpha = L^{-T} z by
+ * back-substitution. The context's workspace is free again afterwards: any entry may run on the
+ * context between queries, and several fits may live on one context. cap >= 1 is the largest
+ * number of test points solved at once; a mean-and-variance query of more points runs in chunks
+ * of cap rows (rows are independent, so M has no upper limit).
+ * Returns 0, info > 0 on a PosDefException (*out is NULL, the text of the last error names the
+ * matrix), GAPLAC_E_ARG also for cap < 1 or out NULL, GAPLAC_E_OOM when the fit's buffer
+ * ((Np + 128 ceil(cap/128)) Np doubles and a few vectors, Np = roundup(N+1, 128)) does not fit
+ * or ceil(cap/128) > 65535. The context stays usable after every failure. N = 0: a fit of the
+ * empty FiniteGP (logpdf -0, every query returns the prior).
+ * Replaces: posterior(FiniteGP(GP(k), X, noise), y) of AbstractGPs 0.5.12 (src/plotting.jl:8-12,
+ *           CLI/src/select.jl:51-52), the object; the queries below are its mean_and_var. */
+typedef struct gaplac_fit gaplac_fit;
+int gaplac_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                      int32_t T, const gaplac_term* terms, double noise, const double* y,
+                      int64_t cap, gaplac_fit** out);
+/* Frees the fit (NULL: 0). Valid before or after its context's destruction, which frees the
+ * fit's device memory and leaves the handle good for this call only. */
+int gaplac_fit_destroy(gaplac_fit* fit);
+/* N, cap and the evaluation's results; any pointer may be NULL. GAPLAC_E_ARG for a NULL fit. */
+int gaplac_fit_info(const gaplac_fit* fit, int64_t* out_N, int64_t* out_cap, double* out_logpdf,
+                    double* out_logdet, double* out_quad);
+/* alpha = C^{-1} y (N values), as computed at creation. */
+int gaplac_fit_alpha(gaplac_fit* fit, double* out_alpha);
+/* Posterior mean at M test points, matrix-free: mean_j = sum_n k(xs_j, x_n) alpha_n with the
+ * latent kernel (no noise; a NOISE term is 0 across point sets). Nothing of size M x N is
+ * stored and the factor is not read. Any M. */
+int gaplac_fit_mean(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean);
+/* Posterior mean and variance at M test points, the arithmetic of the one-shot posterior entry
+ * without its factorisation: K(xs, X) is written below the kept factor, solved against it
+ * (V^T = K(xs, X) L^{-T}), and mean_j = V^T[j,:] z, var_j = k(xs_j, xs_j) - |V^T[j,:]|^2.
+ * out_mean may be NULL; out_var NULL gives the matrix-free mean entry above.
+ * All three queries: outputs are NaN-filled first; GAPLAC_E_ARG for a NULL fit, a fit whose
+ * context has been destroyed, M < 0, Xs NULL or ldxs < M with M > 0 and D > 0, a NULL output of
+ * positive size; M = 0 writes nothing; a fit of N = 0 gives the prior (mean 0, variance kdiag).
+ * Two identical calls give bitwise identical results. */
+int gaplac_fit_mean_var(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs,
+                        double* out_mean, double* out_var);
+
 /* One draw of the FiniteGP: out = L z with C = K(X) + noise I = L L^T
  * and z the N standard-normal values the caller drew (the host keeps the RNG stream, so a
  * given z gives the same sample as the reference). Replaces: rand(rng, FiniteGP(GP(k), X,
@@ -517,6 +561,14 @@ int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_
  * negative controls); 0: as allocated. Not in the reference. */
 int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws,
                              int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for a fitted posterior with room for cap test rows: the create-time launches
+ * after the evaluation (the tile copy out of the workspace, z, the back-substitution), one
+ * mean-and-variance query of M points in chunks of cap, and one matrix-free mean query of M
+ * points, all against the fit's buffer. short_ws 1: the buffer one element short (the negative
+ * control: the back-substitution's first launch leaves it); 0: as allocated. Not in the
+ * reference. */
+int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_t short_ws,
+                          int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* The same check for gaplac_sparse_elbo_grad: gaplac_plan_check_sparse at Ms = 0, then the
  * gradient's launches: the order-Mz ones against its scratch, alpha and the product kernel against
  * the first workspace and the scratch. short_ws 1: the first workspace one element short; 2: the

@@ -20,6 +20,8 @@
 //   gaplac_plan_check_sparse_joint - the same for the sparse joint entries: the copy of the a rows,
 //                                the covariance launches against the second and third workspace,
 //                                the preloaded factorisation of order Ms, plain or with riding rows;
+//   gaplac_plan_check_fit      - the fitted posterior: the tile copy and back-substitution of its
+//                                creation and its two queries against the fit's own buffer;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
@@ -180,6 +182,20 @@ int main() {
                 }
     EXPECT(gaplac_plan_check_sparse_joint(10, 1, 0, 0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG,
            "sparse joint: Ms = 0 accepted");
+    // the fitted posterior: the create-time copy and back-substitution, one mean-and-variance query
+    // in chunks of cap and one mean query against the fit's buffer; then the buffer one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t N : {1, 5, 127, 128, 129, 300, 1000, 4096, 10239, 10240, 16384})
+            for (int64_t cap : {1, 128, 129, 1024})
+                for (int64_t M : {(int64_t)0, (int64_t)1, cap, cap + 1, 5 * cap + 3})
+                    for (int short_ws : {0, 1}) {
+                        const int rc = gaplac_plan_check_fit(N, cap, M, spw, short_ws, &a, &b, msg, sizeof msg);
+                        EXPECT(rc == 0 && a > 0 && (short_ws ? b >= 1 : b == 0),
+                               "plan_check_fit N=%lld cap=%lld M=%lld spw=%d short_ws=%d: rc %d violations %lld %s",
+                               (long long)N, (long long)cap, (long long)M, spw, short_ws, rc, (long long)b, msg);
+                        ++checks;
+                    }
+    EXPECT(gaplac_plan_check_fit(10, 0, 1, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "fit: cap = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
