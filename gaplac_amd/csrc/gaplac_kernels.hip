@@ -1419,58 +1419,133 @@ using MmaLdsT = double[2][2][KBT][LR];  // the k-chunk staging buffers of tile_m
 typedef MmaLdsT<KB> MmaLds;
 static_assert(sizeof(MmaLds) >= GRAM_LDS * sizeof(double), "gram_tile reuses the staging LDS");
 
+// a pointer every lane of the wave holds alike, as one the compiler keeps in scalar registers
+__device__ __forceinline__ const double* wave_uniform(const double* p) {
+    const uint64_t u = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return (const double*)(((uint64_t)hi << 32) | lo);
+}
+
 template <int KBT = KB>
 __device__ __forceinline__ void tile_mma_neg(const double* __restrict__ P, const double* __restrict__ Q,
                                              int64_t ldp, int kdepth, bool active, d4 (&acc)[4][4],
                                              MmaLdsT<KBT>& sm, int64_t ldq = 0) {
     constexpr int KB = KBT;
+    constexpr int NR = 2 * KB / 4;       // staging rows per wave and chunk
     const int64_t lq = ldq ? ldq : ldp;  // Q in a storage of its own (the sparse gradient's W'); 0: P's
     const int tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6;
+    const int lane = tid & 63;
+    // the wave index and the wave's role as scalars: what derives from threadIdx is divergent
+    // to the compiler, and every staging address below would be vector arithmetic
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool act = __builtin_amdgcn_readfirstlane((int)active) != 0;
     const int wi = w & 1, wj = w >> 1;
     const int fr = lane >> 4, fc = lane & 15;
     // LDS-DMA staging: the chunk's 2 KB rows (KB panel columns of P, then of Q: 128 contiguous
     // rows each) go straight into LDS, one global_load_lds (16 B per lane) per row, wave w
-    // taking rows w, w + 4, ...; no staging registers and no LDS stores in the MFMA stream.
+    // taking rows w, w + 4, ... (NR/2 of P, then NR/2 of Q); no staging registers and no LDS
+    // stores in the MFMA stream. Each row's source is a scalar pointer set up once and stepped
+    // by KB columns per chunk, its LDS destination a scalar, the lane's part one 32-bit offset:
+    // per chunk the wave issues NR DMAs with scalar adds only, no multiplies and no
+    // readfirstlanes (134 -> 88 instructions beside a chunk's 64 MFMAs).
     // P stays unnegated in LDS: the MFMA's B-operand neg modifier (blgp = 2 on f64 MFMA)
-    // makes the chain C - P Q^T, bitwise what staging -P gave (register-staged version: 208
-    // VGPRs, 0.794 / 0.833 of peak at the 16k / 64k shapes alone; this one 189 VGPRs, 0.819 /
-    // 0.852, tools/bulk_probe.hip, profiles/r04y_bulk_probe.txt).
-    auto issue = [&](int ch, int buf) {
+    // makes the chain C - P Q^T, bitwise what staging -P gave.
+    const double* src[NR];
+    const uint32_t loff0 = 16u * (uint32_t)lane;  // the lane's 16 bytes of a row
 #pragma unroll
-        for (int it = 0; it < 2 * KB / 4; ++it) {
-            const int t = w + 4 * it, o = t / KB, r = t % KB;
-            const double* src = (o ? Q : P) + (int64_t)(ch * KB + r) * (o ? lq : ldp) + 2 * lane;
-            __builtin_amdgcn_global_load_lds((GlobalCPtr)src, (LdsPtr)&sm[buf][o][r][0], 16, 0, 0);
+    for (int it = 0; it < NR; ++it) {
+        const int o = 4 * it / KB, r = w + 4 * it % KB;
+        src[it] = wave_uniform(o ? Q : P) + (int64_t)r * (o ? lq : ldp);
+    }
+    const int64_t stp = KB * ldp, stq = KB * lq;
+    auto issue = [&](int buf) {  // the next chunk not yet staged, into buffer buf
+        // (the empty asms keep each row pointer whole in its scalar pair and the offset's
+        // widening in the block of its use: only then does the compiler pick the scalar-base
+        // form of the load, with no vector add and no address pair)
+        uint32_t loff = loff0;
+        asm volatile("" : "+v"(loff));
+#pragma unroll
+        for (int it = 0; it < NR; ++it) {
+            const int o = 4 * it / KB, r = w + 4 * it % KB;
+            const char* row = (const char*)src[it];
+            asm volatile("" : "+s"(row));
+            __builtin_amdgcn_global_load_lds((GlobalCPtr)(row + loff), (LdsPtr)&sm[buf][o][r][0], 16, 0, 0);
+            src[it] += o ? stq : stp;
         }
     };
+    auto frags = [&](int buf, int ks, double (&fa)[4], double (&fb)[4]) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            fa[m] = sm[buf][1][ks + fr][64 * wj + 16 * m + fc];
+            fb[m] = sm[buf][0][ks + fr][64 * wi + 16 * m + fc];
+        }
+    };
+    auto mma = [&](const double (&fa)[4], const double (&fb)[4]) {
+#pragma unroll
+        for (int mj = 0; mj < 4; ++mj)
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                acc[mi][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mj], fb[mi], acc[mi][mj], 0, 0, 2);
+    };
     const int NCH = kdepth / KB;
-    issue(0, 0);
+    issue(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int ch = 0; ch < NCH; ++ch) {
+    // The chunk boundary under the last k-step's MFMAs. Chunk ch + 1 is in flight into the
+    // other buffer while chunk ch is multiplied; when the last k-step's fragments are in
+    // registers the wave is done reading this buffer (lgkmcnt) and its own rows of the other
+    // have landed (vmcnt), so the workgroup meets at the barrier BEFORE that k-step's 16 MFMAs
+    // and issues, among them, the DMA of chunk ch + 2 into the buffer just left and the reads
+    // of chunk ch + 1's first k-step. Inactive waves run the same barriers and DMA issues.
+    if (NCH > 1) issue(1);
+    double ha[4], hb[4];  // the first k-step's fragments of the chunk to come
+    if (act) frags(0, 0, ha, hb);
+    auto chunk = [&](int ch, auto stage) {
+        constexpr bool STAGE = decltype(stage)::value;
         const int buf = ch & 1;
-        if (ch + 1 < NCH) issue(ch + 1, buf ^ 1);  // the buffer every wave left at the last barrier
-        if (active) {
+        double ta[4], tb[4];  // the last k-step's fragments, multiplied after the barrier
+        if (act) {
+            mma(ha, hb);
 #pragma unroll
-            for (int ks = 0; ks < KB; ks += 4) {
-                double fa[4], fb[4];
+            for (int ks = 4; ks < KB - 4; ks += 4) {
+                frags(buf, ks, ta, tb);
+                mma(ta, tb);
+            }
+            frags(buf, KB - 4, ta, tb);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (act) {
+            // (the fence is in this branch alone, so that the DMA issues stay in it, among the
+            // MFMAs, and are not merged with the other branch's ahead of the branch)
+            __builtin_amdgcn_sched_barrier(0);
+            if (STAGE) issue(buf);
+            if (STAGE || ch + 1 < NCH) frags(buf ^ 1, 0, ha, hb);
+            mma(ta, tb);
+            if (STAGE) {
+                // one DMA, then one fragment read, behind each of the first MFMAs (the compiler
+                // would issue them in one clump ahead of the first)
 #pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    fa[m] = sm[buf][1][ks + fr][64 * wj + 16 * m + fc];
-                    fb[m] = sm[buf][0][ks + fr][64 * wi + 16 * m + fc];
+                for (int i = 0; i < NR; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
                 }
 #pragma unroll
-                for (int mj = 0; mj < 4; ++mj)
-#pragma unroll
-                    for (int mi = 0; mi < 4; ++mi)
-                        acc[mi][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[mj], fb[mi], acc[mi][mj], 0, 0, 2);
+                for (int i = 0; i < 4; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 16 - NR - 4, 0);
             }
+        } else {
+            if (STAGE) issue(buf);
         }
-        // the next chunk landed (every wave's own DMA), then visible to all waves
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
+    };
+    int ch = 0;
+    for (; ch + 2 < NCH; ++ch) chunk(ch, std::true_type{});
+    for (; ch < NCH; ++ch) chunk(ch, std::false_type{});  // nothing left to stage
 }
 
 template <int KBT = KB>
@@ -1517,8 +1592,9 @@ __device__ __forceinline__ void tile_syrk_body(const BulkArgs& a, int b) {
     }
 }
 
-// One tile per workgroup, 189 VGPRs (208 with register staging): two resident bulk
-// workgroups leave 134 registers per SIMD lane, more than the 96 a quadrant chain kernel needs.
+// One tile per workgroup, 175 VGPRs (189 before the staging addresses were hoisted, 208 with
+// register staging): two resident bulk workgroups leave 160 registers per SIMD lane, more than
+// the 96 a quadrant chain kernel needs.
 // Diagnostic build only (-DGAPLAC_CLOCK=1): each workgroup of the bulk tile kernels adds
 // its shader cycles (s_memtime) and 100 MHz ticks (s_memrealtime) to its launch's KTime
 // slot; the host prints the clock held per launch (MI355X_MICROARCH.md 'DVFS give-back'
