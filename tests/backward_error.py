@@ -59,6 +59,10 @@ design_bound: what the HIP factorisation may reach by its design (gaplac_kernels
 substitution_model is the numpy model of point 2: a right-looking Cholesky, 16 columns at a time,
 whose panel is B @ inv(L_bb).T; it lets the CPU suite show that the plain check fails where the
 design predicts and that the design check holds.
+
+ld_logpdf and ld_logpdf_grad are the long-double references of the forward checks (logpdf; alpha,
+dparam, dnoise), lapack_grad is fp64 LAPACK's gradient on a given C (the yardstick), and
+alpha_forward_bound carries the design bounds forward into the gradient's alpha = Y z.
 """
 import warnings
 
@@ -155,13 +159,18 @@ def _tri_inverse_ld(T):
         from tests import hp_oracle as H
         Ti = H.MP.inverse(H.MP.matrix(T.tolist()))
         return np.array([[float(Ti[i, j]) for j in range(n)] for i in range(n)])
-    Tl = T.astype(LD)
+    return np.asarray(_tri_inverse_long(T.astype(LD)), dtype=np.float64)
+
+
+def _tri_inverse_long(Tl):
+    """The same inverse of a long-double lower triangular matrix, kept in long double."""
+    n = Tl.shape[0]
     X = np.zeros((n, n), dtype=LD)
     for i in range(n):
         rhs = -(Tl[i, :i] @ X[:i])
         rhs[i] += 1
         X[i] = rhs / Tl[i, i]
-    return np.asarray(X, dtype=np.float64)
+    return X
 
 
 def design_terms(L, nb=DB):
@@ -377,11 +386,7 @@ def ld_logpdf(C, v, refine=True):
     L = ld_cholesky(C)
     N = C.shape[0]
     vl = v.astype(LD)
-    Li = np.zeros((N, N), dtype=LD)                   # L^-1, row by row
-    for i in range(N):
-        row = -(L[i, :i] @ Li[:i])
-        row[i] += 1
-        Li[i] = row / L[i, i]
+    Li = _tri_inverse_long(L)                         # L^-1, row by row
     z = Li @ vl
     logdet = 2 * np.sum(np.log(np.diag(L)))
     quad = z @ z
@@ -395,6 +400,95 @@ def ld_logpdf(C, v, refine=True):
         av = -_exact_residual(np.zeros((1, 1)), Sa, _slices(vl[None, :]))[0, 0]
         quad = av + a @ rho
     return -(N * LOG2PI + logdet + quad) / 2, logdet, quad
+
+
+# ----------------------------------------------------------------------- long-double reference gradient
+def grad_derivatives(X, terms):
+    """[dC/dparam_t] in fp64, as oracle.restatement.logpdf_grad forms them: term_derivative times the
+    other terms of the product group."""
+    terms = list(terms)
+    out = []
+    for t, (kind, col, param, group) in enumerate(terms):
+        dK = R.term_derivative(X, kind, col, param)
+        for s, (k2, c2, p2, g2) in enumerate(terms):
+            if s != t and g2 == group:
+                dK = dK * R.term_matrix(X, k2, c2, p2)
+        out.append(dK)
+    return out
+
+
+def ld_logpdf_grad(C, X, terms, v, with_scale=False):
+    """(alpha, dparam, dnoise) of log N(v | 0, C) in long double, C the fp64 covariance of the formula
+    `terms` on the rows of X (dv = -alpha):
+        alpha = C^-1 v,   dparam_t = 1/2 sum_ij (alpha_i alpha_j - C^-1_ij) dC_ij,   dnoise = 1/2 tr(...),
+    with C^-1 = L^-T L^-1 from ld_cholesky and _tri_inverse_long, every product and sum in long double,
+    and dC = grad_derivatives (fp64 data, taken as exact). The solve for alpha is refined to first
+    order as in ld_logpdf: alpha += M^-1 (v - C alpha) with the residual formed exactly. What the
+    stored factor leaves in C^-1 is cond(C) N 2^-64 of it, 2^-11 of what fp64 LAPACK loses.
+    with_scale: also the magnitudes 1/2 sum (|alpha_i alpha_j| + |C^-1_ij|) |dC_ij| per parameter and
+    1/2 sum_i (alpha_i^2 + |C^-1_ii|) for the noise (oracle.restatement.logpdf_grad_scale's), and
+    |C^-1| (for alpha_forward_bound), as fp64."""
+    L = ld_cholesky(C)
+    vl = v.astype(LD)
+    Li = _tri_inverse_long(L)
+    alpha = Li.T @ (Li @ vl)
+    rho = _exact_residual(vl[:, None], _slices(C), _slices(alpha[None, :]))[:, 0]          # v - C alpha
+    alpha = alpha + Li.T @ (Li @ rho)
+    Cinv = Li.T @ Li
+    W = np.outer(alpha, alpha) - Cinv
+    dCs = grad_derivatives(X, terms)
+    half = LD(1) / 2
+    dparam = np.array([half * np.sum(W * dC.astype(LD)) for dC in dCs], dtype=LD)
+    dnoise = half * np.sum(np.diag(W))
+    if not with_scale:
+        return alpha, dparam, dnoise
+    A = np.abs(np.outer(alpha, alpha)) + np.abs(Cinv)
+    scale = np.array([float(half * np.sum(A * np.abs(dC).astype(LD))) for dC in dCs])
+    return alpha, dparam, dnoise, scale, float(half * np.sum(np.diag(A))), np.asarray(np.abs(Cinv), dtype=np.float64)
+
+
+def alpha_forward_bound(L, z, alpha, Cinv_abs):
+    """Entrywise bound of |alpha_hat - C^-1 v| for the gradient's alpha_hat = fl(Y z) (alpha_partial_kernel),
+    Y the identity rows carried through the factorisation (Y = L^-T), from the design bounds above, to
+    first order. With L L^T = C + E, L z = v + e and a = L^-T z:  C a = v + e - E a, so
+        a - C^-1 v = C^-1 (e - E a),      |E| <= design_bound,  |e| <= design_bound_solve.
+    Row i of Y goes through the riding row's arithmetic with the right-hand side e_i (trsm_rows: the
+    16 x 16 explicit inverses, point 2): L y_i^T = e_i + r_i with design_bound_solve's form, so
+    Y = (I + R) L^-T,  |R|[i, J_b] <= gamma_{N+4} (|Y||L^T|)[i, J_b] + C_SUB gamma_16 T_b |y_i[J_b]|.
+    The product is a sum of N terms however it is grouped (four accumulators per 512 columns, then
+    the chunks): alpha_hat = Y z + d, |d| <= gamma_{N+4} |Y||z|. Together
+        |alpha_hat - C^-1 v| <= |C^-1| (|e| + |E||a|) + |R||a| + gamma_{N+4} |Y||z|,
+    evaluated with alpha_hat for a and the inverse of the returned L for Y, times 1.01 for what first
+    order drops (cond(C) gamma_N of it: below 1e-3 on the designed inputs). The first term is the
+    forward error any Cholesky solve is allowed (LAPACK's has gamma_{N+1} |L||L^T| for |E|); the factor's
+    substitution term inside design_bound is what the explicit inverses add to it."""
+    N = L.shape[0]
+    a = np.abs(alpha)
+    Labs = np.abs(L)
+    E = design_bound(L, Labs @ Labs.T)
+    e = design_bound_solve(L, z, Labs @ np.abs(z))
+    Y = np.abs(_tri_inverse(L)).T
+    Ra = gamma(N + 1 + GAMMA_EXTRA) * (Y @ (Labs.T @ a))
+    for j0, j1, T in design_terms(L):
+        Ra += C_SUB * gamma(DB) * (Y[:, j0:j1] @ (T.T @ a[j0:j1]))
+    return 1.01 * (Cinv_abs @ (e + E @ a) + Ra + gamma(N + 1 + GAMMA_EXTRA) * (Y @ np.abs(z)))
+
+
+def lapack_grad(C, X, terms, v):
+    """(alpha, dparam, dnoise) in fp64 with oracle.restatement.logpdf_grad_potri's arithmetic (dpotrf,
+    cho_solve, dpotri, vdot) on a given C. Raises numpy.linalg.LinAlgError where dpotrf finds C not
+    positive definite."""
+    from scipy.linalg import lapack
+    U, info = lapack.dpotrf(C, lower=0, clean=1, overwrite_a=0)
+    if info:
+        raise np.linalg.LinAlgError(f"dpotrf info = {info}")
+    alpha = scipy.linalg.cho_solve((U, False), v, check_finite=False)
+    Cinv, info = lapack.dpotri(U, lower=0, overwrite_c=1)
+    Cinv = np.triu(Cinv) + np.triu(Cinv, 1).T
+    W = np.outer(alpha, alpha)
+    W -= Cinv
+    dparam = np.array([0.5 * float(np.vdot(W, dK)) for dK in grad_derivatives(X, terms)])
+    return alpha, dparam, 0.5 * float(np.trace(W))
 
 
 # --------------------------------------------------------------------------------------------- inputs

@@ -1,7 +1,8 @@
 """(CPU) The backward-error checks of tests/backward_error.py on LAPACK and on the numpy model of
 the inverse-based substitution: the plain bound admits LAPACK on every designed input, the design
 bound admits the model, the plain bound refuses the model where the design predicts, the design bound
-refuses a perturbed factor, and the long-double reference logpdf is as exact as it is taken to be.
+refuses a perturbed factor, and the long-double references (logpdf, gradient) are as exact as they are
+taken to be; the forward bound of the gradient's alpha admits LAPACK and the model.
 
 Figures of this file (worst entry / bound, 60 designed inputs: 5 designs x 4 noise levels x 3 sizes):
   LAPACK / plain_bound: factor 0.013 - 0.093, solve 0.002 - 0.056;
@@ -176,3 +177,107 @@ def test_long_double_reference_against_50_digits():
     print(f"BACKWARD cpu yardstick: |ld - exact| / |LAPACK - exact| = {float(errs[True] / lap):.3g} "
           f"(unrefined {float(errs[False] / lap):.3g}), LAPACK's relative error {float(lap / abs(ref)):.3g}")
     assert lap > 0 and errs[True] <= H.mpf(10) ** -6 * lap
+
+
+# ------------------------------------------------------------------- the long-double reference gradient
+PRODUCT = [(B.SQEXP, 0, 1.3, 0), (B.LINEAR, 1, 0.4, 0), (B.CAT, 2, 0.0, 0), (B.OU, 0, 2.5, 1), (B.NOISE, -1, 0.2, 2)]
+
+
+@pytest.mark.skipif(not B.HAVE_LD, reason="no 64-bit-significand long double")
+@pytest.mark.parametrize("N", [1, 2, 3])
+@pytest.mark.parametrize("noise", [0.1, 1e-4])
+def test_long_double_gradient_against_50_digits(N, noise):
+    """ld_logpdf_grad against hp_oracle.grad_from (50 digits) on the same fp64 C and dC, a product-group
+    formula: every output within 64 cond(C) 2^-64 of (|ref| + scale) (a few dozen roundings at 2^-64,
+    which the inverse multiplies by cond(C) at most), alpha of max |alpha|."""
+    rng = np.random.default_rng(40 + N)
+    X = np.column_stack([rng.uniform(0, 2, N), rng.normal(size=N), rng.integers(0, 2, N).astype(float)])
+    v = rng.normal(size=N)
+    C = R.gram(X, PRODUCT, noise)
+    dCs = B.grad_derivatives(X, PRODUCT)
+    alpha, dp, dn, sc, scn, _ = B.ld_logpdf_grad(C, X, PRODUCT, v, with_scale=True)
+    rdv, rdp, rdn, rsc, rscn = H.grad_from(H.MP.matrix(C.tolist()), [H.MP.matrix(d.tolist()) for d in dCs], v)
+    tol = 64 * np.linalg.cond(C) * 2.0 ** -64
+
+    def err(x, ref):                                   # |x - ref| of a long double against 50 digits
+        hi = float(x)
+        return abs(H.mpf(hi) + H.mpf(float(x - np.longdouble(hi))) - ref)
+
+    assert max(err(alpha[i], -rdv[i]) for i in range(N)) <= tol * max(abs(a) for a in rdv)
+    for t in range(len(PRODUCT)):
+        assert err(dp[t], rdp[t]) <= tol * (abs(rdp[t]) + rsc[t]), (t, dp[t], rdp[t])
+        assert abs(sc[t] - float(rsc[t])) <= 1e-14 * float(rsc[t])
+    assert err(dn, rdn) <= tol * (abs(rdn) + rscn)
+    assert abs(scn - float(rscn)) <= 1e-14 * float(rscn)
+
+
+@pytest.mark.skipif(not B.HAVE_LD, reason="no 64-bit-significand long double")
+@pytest.mark.parametrize("name", B.DESIGNS)
+def test_long_double_gradient_against_lapack(name):
+    """N = 129, noise 1e-6: fp64 LAPACK (logpdf_grad_potri's arithmetic; lapack_grad is bitwise that)
+    is within its own expected error of the long-double gradient, cond(C) 2^-53 of the scale."""
+    X, terms, noise, v = B.designed_input(name, 1e-6, 129)
+    C = R.gram(X, terms, noise)
+    alpha, dp, dn, sc, scn, Ci = B.ld_logpdf_grad(C, X, terms, v, with_scale=True)
+    la, ldp, ldn = B.lapack_grad(C, X, terms, v)
+    _, pdv, pdp, pdn = R.logpdf_grad_potri(X, terms, noise, v)
+    assert np.array_equal(-la, pdv) and np.array_equal(ldp, pdp) and ldn == pdn
+    rsc, rscn = R.logpdf_grad_scale(X, terms, noise, v)
+    bound = np.linalg.cond(C) * B.U
+    assert np.all(np.abs(rsc - sc) <= 10 * bound * sc) and abs(rscn - scn) <= 10 * bound * scn
+    ea = float(np.max(np.abs(la - alpha)) / np.max(np.abs(alpha)))
+    ep = B.worst_ratio(np.abs(np.asarray(ldp - dp, dtype=np.float64)), sc)
+    en = float(abs(ldn - dn)) / scn
+    print(f"BACKWARD cpu gradient yardstick {name}-1e-06-129: cond {bound / B.U:.3g}; LAPACK's error over "
+          f"cond u scale: alpha {ea / bound:.3g}, dparam {ep / bound:.3g}, dnoise {en / bound:.3g}")
+    assert ea <= bound and ep <= bound and en <= bound
+
+
+@pytest.mark.skipif(not B.HAVE_LD, reason="no 64-bit-significand long double")
+@pytest.mark.parametrize("key", [("unif", 1e-8, 300), ("dates", 1e-6, 300), ("composite", 0.1, 300)], ids=B.input_name)
+def test_alpha_forward_bound_on_lapack_and_model(key):
+    """alpha_forward_bound admits alpha = Y z with LAPACK's factor and with the model's (the explicit
+    16 x 16 inverses), with the slack of a worst-case bound (measured: worst entry / bound 2e-4 to
+    2e-3). On unif-1e-08-300 the model's alpha is 55 times LAPACK's error from the long-double alpha, by
+    substitution and by Y z alike: the loss is the factor's, not the route's."""
+    X, terms, noise, v = B.designed_input(*key)
+    C = R.gram(X, terms, noise)
+    alpha, _, _, _, _, Ci = B.ld_logpdf_grad(C, X, terms, v, with_scale=True)
+    errs = {}
+    for name, L, z in (("lapack", np.linalg.cholesky(C), None), ("model", B.substitution_model(C), None)):
+        z = (scipy.linalg.solve_triangular(L, v, lower=True, check_finite=False) if name == "lapack"
+             else B.substitution_model_solve(L, v))
+        a = B._tri_inverse(L).T @ z
+        e = np.abs(np.asarray(a - alpha, dtype=np.float64))
+        r = B.worst_ratio(e, B.alpha_forward_bound(L, z, a, Ci))
+        errs[name] = float(e.max())
+        print(f"BACKWARD cpu alpha forward {B.input_name(key)} {name}: worst/bound {r:.3g}, max error {e.max():.3g}")
+        assert r <= 1.0, (name, r)
+        if name == "model":
+            bs = scipy.linalg.solve_triangular(L, z, lower=True, trans="T", check_finite=False)
+            errs["model_subst"] = float(np.max(np.abs(np.asarray(bs - alpha, dtype=np.float64))))
+    if key == ("unif", 1e-8, 300):
+        assert errs["model"] > 10 * errs["lapack"] and errs["model_subst"] > 10 * errs["lapack"], errs
+    if noise == 0.1:      # well conditioned: the bound is far below 1e-9 and sees one entry 1e-8 off
+        L = B.substitution_model(C)
+        z = B.substitution_model_solve(L, v)
+        a = B._tri_inverse(L).T @ z
+        i = int(np.argmax(np.abs(a)))
+        a[i] *= 1.0 + 1e-8
+        e = np.abs(np.asarray(a - alpha, dtype=np.float64))
+        assert e[i] > B.alpha_forward_bound(L, z, a, Ci)[i]
+
+
+def test_gradient_inputs_are_admitted():
+    """tests/test_gpu_backward.py skips a gradient input that LAPACK finds not positive definite; at most
+    a quarter may go that way. Here, with LAPACK alone on the restatement's C: none does."""
+    keys = [k for k in KEYS if k[2] in (300, 700)]
+    bad = []
+    for key in keys:
+        X, terms, noise, v = B.designed_input(*key)
+        try:
+            np.linalg.cholesky(R.gram(X, terms, noise))
+        except np.linalg.LinAlgError:
+            bad.append(key)
+    assert len(keys) == 40 and 4 * len(bad) <= len(keys), bad
+    assert not bad
