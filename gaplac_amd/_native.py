@@ -13,6 +13,7 @@ LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgaplac_hip.so")
 
 SQEXP, OU, LINEAR, CAT, NOISE = 1, 2, 3, 4, 5
+LIK_GAUSSIAN, LIK_BERNOULLI, LIK_POISSON = 0, 1, 2  # GAPLAC_LIK_*
 KIND_NAMES = {SQEXP: "SQEXP", OU: "OU", LINEAR: "LINEAR", CAT: "CAT", NOISE: "NOISE"}
 MAX_TERMS = 16
 
@@ -38,6 +39,8 @@ EXPORTED = (
     "gaplac_fit_alpha",
     "gaplac_fit_mean",
     "gaplac_fit_mean_var",
+    "gaplac_laplace_logpdf",
+    "gaplac_laplace_posterior_mean_var",
     "gaplac_rand",
     "gaplac_logpdf_multi",
     "gaplac_logpdf_multi_device",
@@ -63,6 +66,7 @@ EXPORTED = (
     "gaplac_plan_check_schedule",
     "gaplac_plan_check_joint",
     "gaplac_plan_check_fit",
+    "gaplac_plan_check_laplace",
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
     "gaplac_plan_check_sparse_grad_z",
@@ -187,6 +191,15 @@ def load() -> ctypes.CDLL:
     lib.gaplac_fit_mean_var.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.gaplac_plan_check_fit.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
                                           POINTER(c_int64), c_char_p, c_int64]
+    # (jitter in the place of noise; then lik, lik_param, y, max_iter, tol, a0)
+    laplace = [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Term), c_double, c_int32, c_double,
+               c_void_p, c_int32, c_double, c_void_p]
+    status = [POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]
+    lib.gaplac_laplace_logpdf.argtypes = laplace + [_DP, c_void_p, c_void_p] + status
+    lib.gaplac_laplace_posterior_mean_var.argtypes = laplace + [c_int64, c_void_p, c_int64, _DP, c_void_p,
+                                                                c_void_p] + status
+    lib.gaplac_plan_check_laplace.argtypes = [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                              c_char_p, c_int64]
     lib.gaplac_rand.argtypes = common + [c_void_p]
     # (the matrix forms take R, the matrix and its leading dimension where `common` ends in v)
     multi = common[:-1] + [c_int64, c_void_p, c_int64]

@@ -336,9 +336,158 @@ class FiniteApproxPosteriorGP(FinitePosteriorGP):
         return self._ctx(ctx).sparse_posterior_logpdf(*self._args(), ys, full=full)
 
 
+# ---- Laplace approximation, in the shape of ApproximateGPs.jl ----
+class BernoulliLikelihood:
+    """GPLikelihoods.BernoulliLikelihood() with its default logistic link: y in {0, 1}."""
+    code, param = backend._native.LIK_BERNOULLI, 0.0
+
+    def __repr__(self):
+        return "BernoulliLikelihood()"
+
+
+class PoissonLikelihood:
+    """GPLikelihoods.PoissonLikelihood() with its default exp link: y a count."""
+    code, param = backend._native.LIK_POISSON, 0.0
+
+    def __repr__(self):
+        return "PoissonLikelihood()"
+
+
+class GaussianLikelihood:
+    """GPLikelihoods.GaussianLikelihood(var): the approximation is then exact."""
+    code = backend._native.LIK_GAUSSIAN
+
+    def __init__(self, var):
+        var = float(var)
+        if not (var > 0.0) or not np.isfinite(var):
+            raise F.ArgumentError(f"GaussianLikelihood: the variance {var} must be finite and > 0")
+        self.param = var
+
+    def __repr__(self):
+        return f"GaussianLikelihood({self.param})"
+
+
+_LIKELIHOODS = (BernoulliLikelihood, PoissonLikelihood, GaussianLikelihood)
+
+
+class LatentGP:
+    """AbstractGPs.LatentGP(f, lik, jitter): a GP whose values are seen through the likelihood
+    lik; jitter >= 0 is added to the latent covariance's diagonal."""
+
+    def __init__(self, f: GP, lik, jitter: float = 1e-6):
+        if not isinstance(f, GP):
+            raise F.ArgumentError("LatentGP takes a GP")
+        if not isinstance(lik, _LIKELIHOODS):
+            raise F.ArgumentError("LatentGP: lik must be a BernoulliLikelihood, PoissonLikelihood or GaussianLikelihood")
+        jitter = float(jitter)
+        if not (jitter >= 0.0) or not np.isfinite(jitter):
+            raise F.ArgumentError(f"LatentGP: jitter {jitter} must be finite and >= 0")
+        self.f, self.lik, self.jitter = f, lik, jitter
+
+    def __call__(self, x, obsdim=1):
+        return LatentFiniteGP(self, x, obsdim=obsdim)
+
+
+class LatentFiniteGP:
+    """lgp(x): the latent GP at the rows of x (AbstractGPs.LatentFiniteGP)."""
+
+    def __init__(self, lgp: LatentGP, x, obsdim=1):
+        self.lgp = lgp
+        self.fx = FiniteGP(lgp.f, x, lgp.jitter, obsdim=obsdim)
+        self.lik = lgp.lik
+
+    def __len__(self):
+        return len(self.fx)
+
+
+class LaplaceApproximation:
+    """ApproximateGPs.LaplaceApproximation: Newton's iteration, at most maxiter steps, stopped
+    when the objective changes by no more than tol (1 + |objective|)."""
+
+    def __init__(self, maxiter: int = 100, tol: float = 1e-12):
+        if int(maxiter) != maxiter or int(maxiter) < 1:
+            raise F.ArgumentError(f"LaplaceApproximation: maxiter = {maxiter} must be an integer >= 1")
+        tol = float(tol)
+        if not (tol > 0.0) or not np.isfinite(tol):
+            raise F.ArgumentError(f"LaplaceApproximation: tol = {tol} must be finite and > 0")
+        self.maxiter, self.tol = int(maxiter), tol
+
+
+def _laplace_args(la, lfx, y):
+    if not isinstance(la, LaplaceApproximation) or not isinstance(lfx, LatentFiniteGP):
+        raise F.ArgumentError("expected (LaplaceApproximation(), LatentGP(f, lik, jitter)(x), y)")
+    y = np.asarray(y, dtype=np.float64)
+    if y.ndim != 1 or y.shape[0] != len(lfx):
+        raise F.ArgumentError("DimensionMismatch: length of y does not match the LatentFiniteGP")
+    return y
+
+
+def approx_lml(la: LaplaceApproximation, lfx: LatentFiniteGP, y, ctx: backend.Context | None = None, a0=None,
+               full: bool = False):
+    """ApproximateGPs.approx_lml(la, lfx, y): log q(y | X) of the Laplace approximation
+    (gaplac_laplace_logpdf). a0: a warm start; full=True returns the backend's LaplaceResult."""
+    _gate()
+    y = _laplace_args(la, lfx, y)
+    fx = lfx.fx
+    return (ctx or backend.default_context()).laplace_logpdf(
+        fx.x, fx.terms, fx.noise, lfx.lik.code, y, lik_param=lfx.lik.param, max_iter=la.maxiter, tol=la.tol, a0=a0,
+        full=full)
+
+
+class LaplacePosteriorGP:
+    """posterior(la, lfx, y): the Gaussian approximation of the latent posterior. The mode is found
+    when f_hat (or logq) is first asked for and kept as the warm start of every query; each
+    mean_and_var is one gaplac_laplace_posterior_mean_var call."""
+
+    def __init__(self, la: LaplaceApproximation, lfx: LatentFiniteGP, y, ctx: backend.Context | None = None):
+        self.y = _laplace_args(la, lfx, y)
+        self.la, self.lfx, self.prior, self.ctx = la, lfx, lfx.fx, ctx
+        self._res = None
+
+    def _ctx(self):
+        return self.ctx or backend.default_context()
+
+    def _mode(self):
+        if self._res is None:
+            _gate()
+            self._res = approx_lml(self.la, self.lfx, self.y, ctx=self._ctx(), full=True)
+        return self._res
+
+    @property
+    def f_hat(self):
+        """The mode of the latent posterior at the training inputs."""
+        return self._mode().f
+
+    @property
+    def logq(self):
+        return self._mode().logq
+
+    def mean_and_var(self, x):
+        _gate()
+        X = np.asarray(x, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[:, None]
+        fx, lik = self.prior, self.lfx.lik
+        a0 = self._res.a if self._res is not None and self._res.converged else None
+        return self._ctx().laplace_posterior_mean_var(fx.x, fx.terms, fx.noise, lik.code, self.y, X,
+                                                      lik_param=lik.param, max_iter=self.la.maxiter, tol=self.la.tol,
+                                                      a0=a0)
+
+    def mean(self, x):
+        return self.mean_and_var(x)[0]
+
+    def var(self, x):
+        return self.mean_and_var(x)[1]
+
+
 def posterior(*args, ctx: backend.Context | None = None):
     """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8), or
-    posterior(VFE(f(z)), fx, y): the approximate posterior of the inducing-point approximation."""
+    posterior(VFE(f(z)), fx, y): the approximate posterior of the inducing-point approximation, or
+    posterior(LaplaceApproximation(), lfx, y): the Laplace approximation of a latent GP's."""
+    if args and isinstance(args[0], LaplaceApproximation):
+        if len(args) not in (3, 4):
+            raise F.ArgumentError("posterior(LaplaceApproximation(), lfx, y)")
+        return LaplacePosteriorGP(args[0], args[1], args[2], args[3] if len(args) == 4 else ctx)
     if args and isinstance(args[0], VFE):
         if len(args) not in (3, 4):
             raise F.ArgumentError("posterior(VFE(f(z)), fx, y)")
@@ -410,6 +559,16 @@ def design_matrix(table, vars_) -> np.ndarray:
     return np.column_stack(cols)
 
 
+def _formula_likelihood(spec: F.Spec):
+    """The likelihood object of a formula's slot; None for Gaussian (the FiniteGP path)."""
+    lik = F.likelihood(spec)
+    if isinstance(lik, F.Bernoulli):
+        return BernoulliLikelihood()
+    if isinstance(lik, F.Poisson):
+        return PoissonLikelihood()
+    return None
+
+
 def select_formulae(f1: str, f2: str, table, noise: float = 0.1, ctx: backend.Context | None = None,
                     responses=None):
     """CLI/src/select.jl:21-54 (`select --formulae`): logpdf of two formulas on the same
@@ -417,10 +576,29 @@ def select_formulae(f1: str, f2: str, table, noise: float = 0.1, ctx: backend.Co
     run through one batched call.
     responses: a list of column names scored in place of the formulas' own response (one
     covariate table, many responses): each formula is factored once and scored against all of
-    them (two logpdf_multi calls); the three results are then arrays, one entry per name."""
+    them (two logpdf_multi calls); the three results are then arrays, one entry per name.
+    A formula with `Bernoulli` or `Poisson` in its likelihood slot is scored by approx_lml (the
+    Laplace approximation, jitter 1e-6) in place of logpdf; responses= takes Gaussian formulas only."""
     _gate()
     ctx = ctx or backend.default_context()
     specs = [F.gp_spec(f1), F.gp_spec(f2)]
+    liks = [_formula_likelihood(s) for s in specs]
+    if responses is not None and any(lk is not None for lk in liks):
+        raise F.ArgumentError("select_formulae: responses= scores Gaussian formulas only")
+    if any(lk is not None for lk in liks):
+        # a formula whose likelihood is not Gaussian: log q of its Laplace approximation (latent
+        # jitter 1e-6); a Gaussian formula beside it keeps logpdf at `noise`
+        lps = []
+        for s, lk in zip(specs, liks):
+            gp, vars_ = make_gp(s)
+            X = design_matrix(table, vars_)
+            y = np.asarray(table[F.response(s)], dtype=np.float64)
+            if lk is None:
+                lps.append(logpdf(FiniteGP(gp, X, noise), y, ctx=ctx))
+            else:
+                lps.append(approx_lml(LaplaceApproximation(), LatentGP(gp, lk, 1e-6)(X), y, ctx=ctx))
+        lp1, lp2 = lps
+        return lp1 - lp2, lp1, lp2
     if responses is not None:
         names = list(responses)
         Y = np.column_stack([np.asarray(table[r], dtype=np.float64) for r in names]) if names else None

@@ -39,6 +39,31 @@ def _colmajor(X: np.ndarray) -> np.ndarray:
     return np.asfortranarray(X)
 
 
+_LIK_CODES = {"gaussian": _native.LIK_GAUSSIAN, "bernoulli": _native.LIK_BERNOULLI, "poisson": _native.LIK_POISSON}
+
+
+def likelihood_code(lik) -> int:
+    """GAPLAC_LIK_* of a likelihood given by name (any case) or by code; an unknown name is an
+    ArgumentError, an unknown code is left to the library (GAPLAC_E_KIND)."""
+    if isinstance(lik, str):
+        try:
+            return _LIK_CODES[lik.lower()]
+        except KeyError:
+            raise ArgumentError(f"unknown likelihood {lik!r}; expected one of {sorted(_LIK_CODES)}") from None
+    return int(lik)
+
+
+class LaplaceResult:
+    """What gaplac_laplace_logpdf returns: log q, the mode f, a = K^{-1} f, the Newton steps taken
+    and whether the iteration met its tolerance."""
+
+    def __init__(self, logq: float, f: np.ndarray, a: np.ndarray, iters: int, converged: bool):
+        self.logq, self.f, self.a, self.iters, self.converged = logq, f, a, iters, converged
+
+    def __repr__(self):
+        return f"LaplaceResult(logq={self.logq!r}, iters={self.iters}, converged={self.converged})"
+
+
 class Context:
     """One device, one persistent workspace (gaplac_ctx)."""
 
@@ -195,6 +220,74 @@ class Context:
             mean.ctypes.data_as(c_void_p), var.ctypes.data_as(c_void_p),
         )
         self._check(rc)
+        return mean, var
+
+    # ---- Laplace approximation (gaplac_laplace_logpdf / _posterior_mean_var) ----
+    def _laplace_args(self, X, terms, jitter, lik, y, lik_param, max_iter, tol, a0):
+        Xc = _colmajor(X)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, D = Xc.shape
+        if y.ndim != 1 or y.shape[0] != N:
+            raise ArgumentError(f"length of y ({y.shape[0] if y.ndim else 0}) != N ({N})")
+        if a0 is not None:
+            a0 = np.ascontiguousarray(a0, dtype=np.float64)
+            if a0.shape != (N,):
+                raise ArgumentError(f"a0 has shape {a0.shape}, expected ({N},)")
+        terms = list(terms)
+        keep = (Xc, y, a0, term_array(terms))
+        args = [self.h, N, D, Xc.ctypes.data_as(c_void_p), max(N, 1), len(terms), keep[3], float(jitter),
+                likelihood_code(lik), float(lik_param), y.ctypes.data_as(c_void_p), int(max_iter), float(tol),
+                a0.ctypes.data_as(c_void_p) if a0 is not None else None]
+        return keep, N, D, args
+
+    @staticmethod
+    def _laplace_warn(converged: bool, iters: int):
+        if not converged:
+            import warnings
+
+            warnings.warn(f"the Laplace approximation's Newton iteration did not converge in {iters} step(s); "
+                          "the results are those of the last iterate", RuntimeWarning, stacklevel=3)
+
+    def laplace_logpdf(self, X, terms, jitter: float, lik, y, lik_param: float = 0.0, max_iter: int = 100,
+                       tol: float = 1e-12, a0=None, full: bool = False):
+        """log q(y | X), the Laplace approximation of the marginal likelihood of a latent GP with
+        covariance K(X) + jitter I under the likelihood lik ("bernoulli", "poisson", "gaussian" or a
+        LIK_* code; lik_param: the Gaussian's variance). full=True returns a LaplaceResult with
+        .logq .f .a .iters .converged; a (= K^{-1} f at the mode) is a warm start a0 for a later call.
+        A RuntimeWarning when the iteration did not converge within max_iter steps."""
+        keep, N, _, args = self._laplace_args(X, terms, jitter, lik, y, lik_param, max_iter, tol, a0)
+        logq = c_double()
+        f = np.empty(N, dtype=np.float64)
+        a = np.empty(N, dtype=np.float64)
+        iters, conv, info = c_int32(), c_int32(), c_int64()
+        rc = self.lib.gaplac_laplace_logpdf(*args, byref(logq), f.ctypes.data_as(c_void_p), a.ctypes.data_as(c_void_p),
+                                            byref(iters), byref(conv), byref(info))
+        self._check(rc)
+        self._laplace_warn(bool(conv.value), iters.value)
+        if full:
+            return LaplaceResult(logq.value, f, a, iters.value, bool(conv.value))
+        return logq.value
+
+    def laplace_posterior_mean_var(self, X, terms, jitter: float, lik, y, Xs, lik_param: float = 0.0,
+                                   max_iter: int = 100, tol: float = 1e-12, a0=None, full: bool = False):
+        """(mean, var) of the Laplace approximation's latent posterior at the rows of Xs; full=True
+        returns (mean, var, logq, iters, converged)."""
+        keep, N, D, args = self._laplace_args(X, terms, jitter, lik, y, lik_param, max_iter, tol, a0)
+        Xsc = _colmajor(Xs)
+        M = Xsc.shape[0]
+        if Xsc.shape[1] != D:
+            raise ArgumentError(f"test inputs have {Xsc.shape[1]} columns, training inputs {D}")
+        logq = c_double()
+        mean = np.empty(M, dtype=np.float64)
+        var = np.empty(M, dtype=np.float64)
+        iters, conv, info = c_int32(), c_int32(), c_int64()
+        rc = self.lib.gaplac_laplace_posterior_mean_var(
+            *args, M, Xsc.ctypes.data_as(c_void_p), max(M, 1), byref(logq), mean.ctypes.data_as(c_void_p),
+            var.ctypes.data_as(c_void_p), byref(iters), byref(conv), byref(info))
+        self._check(rc)
+        self._laplace_warn(bool(conv.value), iters.value)
+        if full:
+            return mean, var, logq.value, iters.value, bool(conv.value)
         return mean, var
 
     def fit(self, X, terms, noise: float, y, cap: int = 1024) -> "Fit":

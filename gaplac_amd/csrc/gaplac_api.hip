@@ -278,6 +278,10 @@ struct gaplac_ctx {
     uint32_t* glist = nullptr;
     size_t glist_elems = 0;
     int glist_m = -1, glist_blocks = 0;
+    // Laplace approximation: every vector of the Newton iteration, the partial
+    // sums and the matrix-free products' scratch in one buffer (LapDims)
+    double* lap = nullptr;
+    size_t lap_elems = 0;
 };
 
 namespace {
@@ -348,7 +352,7 @@ std::vector<Buf> ctx_buffers(gaplac_ctx* c) {
                        large(&c->sp_part, &c->sp_part_elems), large(&c->sg, &c->sg_elems),
                        large(&c->sg_dinv, &c->sg_dinv_elems), large(&c->sg_v, &c->sg_v_elems),
                        large(&c->sgz, &c->sgz_elems), large(&c->C, &c->C_elems),
-                       large(&c->sj_rows, &c->sj_rows_elems)};
+                       large(&c->sj_rows, &c->sj_rows_elems), large(&c->lap, &c->lap_elems)};
     for (auto& w : c->bw)
         b.insert(b.end(), {large(&w.A, &w.A_elems), large(&w.Dinv, &w.Dinv_elems), buf(&w.dres), buf(&w.dtp),
                            buf(&w.hres, 0, true), buf(&w.htp, 0, true), buf(&w.ctl), buf(&w.tasks)});
@@ -2931,6 +2935,320 @@ static int fit_mean_var_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t
     return 0;
 }
 
+// ---------------------------------------------------------------------------------
+// Laplace approximation: Newton's iteration on the host, every vector on
+// the device, one factorisation of the prebuilt B per step through eval_device.
+// ---------------------------------------------------------------------------------
+
+// Test points per final factorisation (their rows ride below B); further points take a
+// factorisation of their own per chunk.
+constexpr int64_t LAP_CHUNK = 4096;
+
+// Where the iteration's vectors lie in the context's buffer (offsets in doubles; at / ft, the
+// trial point, last: a buffer one element short is reported by the line search's launch), and
+// the workspace's size: the matrix with the first chunk's riding rows, then u (N values).
+struct LapDims {
+    int64_t Np, nb, nkm, qc, ldq;
+    int nt;
+    int64_t a, f, g, w, sw, b, c, an, fn, diag, part, lpart, out, mean, at, ft, elems;
+    int64_t u, a_elems;  // in the workspace
+};
+static LapDims lap_dims(int64_t N, int64_t M) {
+    LapDims d{};
+    d.Np = round_up(N + 1, NB);
+    d.nt = (int)(d.Np / NB);
+    d.nb = (N + 255) / 256;
+    d.nkm = (N + 255) / 256;
+    d.qc = std::min(M, LAP_CHUNK);
+    d.ldq = d.Np + NB * ((d.qc + NB - 1) / NB);
+    int64_t o = 0;
+    for (int64_t* p : {&d.a, &d.f, &d.g, &d.w, &d.sw, &d.b, &d.c, &d.an, &d.fn, &d.diag}) {
+        *p = o;
+        o += N;
+    }
+    d.part = o;
+    o += d.nkm * std::max(N, d.qc);
+    d.lpart = o;
+    o += 3 * d.nb;
+    d.out = o;
+    o += 4;
+    d.mean = o;
+    o += d.qc;
+    d.at = o;
+    o += N;
+    d.ft = o;
+    o += N;
+    d.elems = o;
+    d.u = d.ldq * d.Np;
+    d.a_elems = d.u + N;
+    return d;
+}
+
+// The stages' launches, run by the entries and walked dry by gaplac_plan_check_laplace. Each runs
+// under one guard: lap_mf_launches under the vectors' buffer alone (launch_fit_mean checks its
+// scratch against the guard's first allocation), the others under the workspace (first), the
+// vectors' buffer (second) and the response matrix (third).
+// The likelihood at (a, f): g, W, sw, b and the sums.
+static void lap_lik_launches(hipStream_t s, const LapDims& d, int64_t N, int lik, double param, const double* y,
+                             double* lap) {
+    launch_laplace_lik(s, N, lik, param, y, lap + d.a, lap + d.f, lap + d.g, lap + d.w, lap + d.sw, lap + d.b,
+                       lap + d.lpart, lap + d.out);
+}
+// out = K(xs, X) v, matrix-free, without K's diagonal part (m points at Xs, ld ldxs).
+static void lap_mf_launches(hipStream_t s, const LapDims& d, int64_t N, int64_t m, const double* X, const double* Xs,
+                            int64_t ldxs, const TermPack* dtp, double* lap, int64_t v, int64_t out) {
+    launch_fit_mean(s, N, m, X, N, lap + v, Xs, ldxs, dtp, lap + d.part, lap + out);
+}
+// c = K b finished, the Gram (ld lda) and B over it with the right-hand side sw c in row N.
+static void lap_build_launches(hipStream_t s, const LapDims& d, int64_t N, int64_t lda, bool finish_c, double* A,
+                               const double* X, const double* y, const TermPack* dtp, double* lap) {
+    if (finish_c) launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.b, lap + d.c);
+    launch_gram(s, A, lda, N, d.nt, X, N, y, dtp, 0, 0, nullptr);
+    launch_laplace_b_build(s, A, lda, N, d.nt, lap + d.sw, lap + d.c);
+}
+// After the factorisation (ld Np): z out of row N, u = L^{-T} z, a+ = b - sw u.
+static void lap_solve_launches(hipStream_t s, const LapDims& d, int64_t N, double* A, double* lap) {
+    launch_copy_z(s, A, d.Np, N, A + d.u);
+    launch_fit_backsub(s, A, d.Np, N, A + d.u);
+    launch_laplace_anew(s, N, lap + d.b, lap + d.sw, A + d.u, lap + d.an);
+}
+// f+ = K a+ finished.
+static void lap_fnew_launches(hipStream_t s, const LapDims& d, int64_t N, double* lap) {
+    launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.an, lap + d.fn);
+}
+static void lap_trial_launches(hipStream_t s, const LapDims& d, int64_t N, int lik, double param, double step,
+                               const double* y, double* lap) {
+    launch_laplace_trial(s, N, lik, param, step, y, lap + d.a, lap + d.f, lap + d.an, lap + d.fn, lap + d.at,
+                         lap + d.ft, lap + d.lpart, lap + d.out);
+}
+// A chunk of m test points (ld m at Xs): the Gram and B with m riding rows' room (ld lda), and the
+// response matrix diag(sw) K(X, xs) (ld N).
+static void lap_query_launches(hipStream_t s, const LapDims& d, int64_t N, int64_t m, int64_t lda, double* A,
+                               const double* X, const double* y, const double* Xs, const TermPack* dtp, double* lap,
+                               double* Y) {
+    lap_build_launches(s, d, N, lda, false, A, X, y, dtp, lap);
+    launch_laplace_cross(s, N, m, X, N, Xs, m, dtp, lap + d.sw, Y, N);
+}
+
+// The diagonal part of K at training point i that the matrix-free product leaves out: every
+// product group with a NOISE term (0 across point sets), at x_i against itself.
+static double host_noise_diag(const TermPack& tp, const double* X, int64_t ldx, int64_t i) {
+    double kd = 0.0, pr = 1.0;
+    bool has = false;
+    for (int t = 0; t < tp.T; ++t) {
+        const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + i];
+        double k = 1.0;
+        if ((tp.kind[t] == GAPLAC_SQEXP || tp.kind[t] == GAPLAC_OU) && !std::isfinite(tp.p[t] * x)) k = NAN;
+        if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
+        if (tp.kind[t] == GAPLAC_NOISE) {
+            k = tp.p[t];
+            has = true;
+        }
+        pr *= k;
+        if (tp.last_in_group[t]) {
+            if (has) kd += pr;
+            pr = 1.0;
+            has = false;
+        }
+    }
+    return kd;
+}
+
+template <typename Launches>
+static int lap_on_ws(gaplac_ctx* ctx, Launches&& launches) {
+    return guarded_on(ctx, ctx->A, ctx->A_elems, ctx->lap, ctx->lap_elems, launches, ctx->dY, ctx->dY_elems);
+}
+template <typename Launches>
+static int lap_on_vectors(gaplac_ctx* ctx, Launches&& launches) {
+    return guarded_on(ctx, ctx->lap, ctx->lap_elems, nullptr, 0, launches);
+}
+
+// {sum log p, a^T f, psi, non-finite W count} of the last likelihood / trial launch.
+static int lap_read_sums(gaplac_ctx* ctx, const LapDims& d, double* h) {
+    HIPCK(ctx, hipMemcpyAsync(h, ctx->lap + d.out, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->s_main));
+    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
+    return 0;
+}
+
+static int lap_bad_w(gaplac_ctx* ctx, int64_t N, double count, int64_t* out_info) {
+    if (out_info) *out_info = 1;
+    return set_err(ctx, 1, "B = I + sqrt(W) K sqrt(W) (order %lld) cannot be formed: W is not finite at %.0f "
+                           "observations (exp(f) overflows)", (long long)N, count);
+}
+
+// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs) and gaplac_laplace_posterior_mean_var.
+static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                        const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
+                        int32_t max_iter, double tol, const double* a0, bool posterior, int64_t M, const double* Xs,
+                        int64_t ldxs, double* out_logq, double* out_f, double* out_a, double* out_mean,
+                        double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
+    if (out_logq) *out_logq = NAN;
+    if (out_iters) *out_iters = 0;
+    if (out_converged) *out_converged = 0;
+    if (out_info) *out_info = 0;
+    for (int64_t i = 0; i < N; ++i) {
+        if (out_f) out_f[i] = NAN;
+        if (out_a) out_a[i] = NAN;
+    }
+    for (int64_t j = 0; posterior && j < M; ++j) {
+        if (out_mean) out_mean[j] = NAN;
+        if (out_var) out_var[j] = NAN;
+    }
+    int rc = check_common(ctx, N, D, X, ldx, 0.0, y);
+    if (rc) return rc;
+    if (posterior && (M < 0 || (M > 0 && D > 0 && (!Xs || ldxs < M))))
+        return set_err(ctx, GAPLAC_E_ARG, "M < 0, or Xs NULL / ldxs < M");
+    if (!out_logq) return set_err(ctx, GAPLAC_E_ARG, "out_logq is NULL");
+    if (lik != GAPLAC_LIK_GAUSSIAN && lik != GAPLAC_LIK_BERNOULLI && lik != GAPLAC_LIK_POISSON)
+        return set_err(ctx, GAPLAC_E_KIND, "unknown likelihood %d", lik);
+    if (!(jitter >= 0.0) || !std::isfinite(jitter))
+        return set_err(ctx, GAPLAC_E_PARAM, "jitter %g must be finite and >= 0", jitter);
+    if (!(tol > 0.0) || !std::isfinite(tol)) return set_err(ctx, GAPLAC_E_PARAM, "tol %g must be finite and > 0", tol);
+    if (max_iter < 1) return set_err(ctx, GAPLAC_E_PARAM, "max_iter = %d < 1", max_iter);
+    if (lik == GAPLAC_LIK_GAUSSIAN && (!(lik_param > 0.0) || !std::isfinite(lik_param)))
+        return set_err(ctx, GAPLAC_E_PARAM, "the Gaussian likelihood's variance %g must be finite and > 0", lik_param);
+    TermPack tp;
+    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
+    for (int64_t i = 0; i < N; ++i) {
+        const double v = y[i];
+        const bool ok = lik == GAPLAC_LIK_BERNOULLI ? (v == 0.0 || v == 1.0)
+                        : lik == GAPLAC_LIK_POISSON ? (std::isfinite(v) && v >= 0.0 && v == std::floor(v))
+                                                    : std::isfinite(v);
+        if (!ok)
+            return set_err(ctx, GAPLAC_E_PARAM, "y[%lld] = %g is outside the likelihood's support", (long long)i, v);
+    }
+    for (int64_t i = 0; a0 && i < N; ++i)
+        if (!std::isfinite(a0[i])) return set_err(ctx, GAPLAC_E_PARAM, "a0[%lld] is not finite", (long long)i);
+    if (N == 0) {  // no observations: log q = 0 and the prior at the test points
+        *out_logq = 0.0;
+        if (out_converged) *out_converged = 1;
+        for (int64_t j = 0; posterior && j < M; ++j) {
+            if (out_mean) out_mean[j] = 0.0;
+            if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
+        }
+        return 0;
+    }
+    tp.noise = jitter;
+    if (!posterior) M = 0;
+    const LapDims d = lap_dims(N, M);
+    if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535)
+        return set_err(ctx, GAPLAC_E_OOM, "more than 65535 tile rows in one call");
+    HIPCK(ctx, hipSetDevice(ctx->device));
+    if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
+    if ((rc = ensure(ctx, &ctx->A, &ctx->A_elems, (size_t)d.a_elems))) return rc;
+    if ((rc = ensure(ctx, &ctx->lap, &ctx->lap_elems, (size_t)d.elems))) return rc;
+    if (d.qc > 0 && (rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)N * (size_t)d.qc))) return rc;
+    hipStream_t s = ctx->s_main;
+    double* const lap = ctx->lap;
+    const double* const dy = ctx->dv;
+    *ctx->htp = tp;
+    HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, s));
+    {
+        std::vector<double> diag((size_t)N);
+        for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = jitter + host_noise_diag(tp, X, ldx, i);
+        HIPCK(ctx, hipMemcpyAsync(lap + d.diag, diag.data(), (size_t)N * 8, hipMemcpyHostToDevice, s));
+        HIPCK(ctx, hipStreamSynchronize(s));  // (diag is the host's: it ends with this block)
+    }
+    // a = a0 and f = K a, or both 0
+    if (a0) {
+        HIPCK(ctx, hipMemcpyAsync(lap + d.a, a0, (size_t)N * 8, hipMemcpyHostToDevice, s));
+        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.a, d.f); })))
+            return rc;
+        if ((rc = lap_on_ws(ctx, [&] { launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.a, lap + d.f); }))) return rc;
+    } else {
+        HIPCK(ctx, hipMemsetAsync(lap + d.a, 0, (size_t)N * 8, s));
+        HIPCK(ctx, hipMemsetAsync(lap + d.f, 0, (size_t)N * 8, s));
+    }
+    double h[4];
+    auto fail_b = [&](int info) {
+        if (out_info) *out_info = info;
+        return set_err(ctx, info, "B = I + sqrt(W) K sqrt(W) (order %lld): its Cholesky factorisation failed at leading "
+                                  "minor %d, which an indefinite matrix cannot cause (B >= I): W or K is not finite",
+                       (long long)N, info);
+    };
+    int iters = 0;
+    bool converged = false;
+    EvalResult r;
+    for (int it = 0; it < max_iter; ++it) {
+        // the likelihood at (a, f); c = K b; K and B; the factorisation
+        if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(s, d, N, lik, lik_param, dy, lap); }))) return rc;
+        if ((rc = lap_read_sums(ctx, d, h))) return rc;
+        if (h[3] > 0.0) return lap_bad_w(ctx, N, h[3], out_info);
+        const double psi_old = h[2];
+        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.b, d.c); })))
+            return rc;
+        if ((rc = lap_on_ws(ctx, [&] { lap_build_launches(s, d, N, d.Np, true, ctx->A, ctx->dX, dy, ctx->dtp, lap); })))
+            return rc;
+        if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}.on_prebuilt(), &r))) return rc;
+        if ((rc = finish(r, nullptr, nullptr, nullptr))) return fail_b(rc);
+        // u = B^{-1} (sw c), a+ = b - sw u, f+ = K a+
+        if ((rc = lap_on_ws(ctx, [&] { lap_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
+        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.an, d.fn); })))
+            return rc;
+        if ((rc = lap_on_ws(ctx, [&] { lap_fnew_launches(s, d, N, lap); }))) return rc;
+        // the step: the first s = 1, 1/2, ... whose psi is finite and no worse than psi_old (to rounding)
+        double step = 1.0, psi_new = NAN;
+        bool accepted = false;
+        for (int hv = 0; hv <= 20 && !accepted; ++hv, step *= 0.5) {
+            if ((rc = lap_on_ws(ctx, [&] { lap_trial_launches(s, d, N, lik, lik_param, step, dy, lap); }))) return rc;
+            if ((rc = lap_read_sums(ctx, d, h))) return rc;
+            psi_new = h[2];
+            accepted = std::isfinite(psi_new) && psi_new >= psi_old - tol * (1.0 + std::fabs(psi_old));
+        }
+        if (!accepted) break;  // no acceptable step: the iterate stays, not converged
+        HIPCK(ctx, hipMemcpyAsync(lap + d.a, lap + d.at, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+        HIPCK(ctx, hipMemcpyAsync(lap + d.f, lap + d.ft, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+        ++iters;
+        if (std::fabs(psi_new - psi_old) <= tol * (1.0 + std::fabs(psi_new))) {
+            converged = true;
+            break;
+        }
+    }
+    // W at the last iterate, B factored once more (with the first chunk of test points riding)
+    if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(s, d, N, lik, lik_param, dy, lap); }))) return rc;
+    if ((rc = lap_read_sums(ctx, d, h))) return rc;
+    if (h[3] > 0.0) return lap_bad_w(ctx, N, h[3], out_info);
+    const double psi = h[2];
+    double logq = NAN;
+    std::vector<double> quad;
+    for (int64_t r0 = 0; r0 == 0 || r0 < M; r0 += LAP_CHUNK) {
+        const int64_t m = std::min(LAP_CHUNK, M - r0);
+        ExtraRows xr;
+        if (m > 0) {
+            const int64_t lda = d.Np + NB * ((m + NB - 1) / NB);
+            if ((rc = upload_test_inputs(ctx, D, m, 0, m, Xs + r0, ldxs))) return rc;
+            if ((rc = lap_on_ws(ctx, [&] {
+                     lap_query_launches(s, d, N, m, lda, ctx->A, ctx->dX, dy, ctx->dXs, ctx->dtp, lap, ctx->dY);
+                 })))
+                return rc;
+            xr = ExtraRows::responses(m, ctx->dY, N);
+        } else {
+            if ((rc = lap_on_ws(ctx, [&] { lap_build_launches(s, d, N, d.Np, false, ctx->A, ctx->dX, dy, ctx->dtp, lap); })))
+                return rc;
+        }
+        if ((rc = eval_device(ctx, N, D, tp, xr.on_prebuilt(), &r))) return rc;
+        if ((rc = finish(r, nullptr, nullptr, nullptr))) return fail_b(rc);
+        if (r0 == 0) logq = psi - 0.5 * r.logdet;
+        if (m > 0) {
+            if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, m, ctx->dX, ctx->dXs, m, ctx->dtp, lap, d.a, d.mean); })))
+                return rc;
+            quad.resize((size_t)m);
+            HIPCK(ctx, hipMemcpyAsync(quad.data(), ctx->mres, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+            if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean + r0, lap + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+            HIPCK(ctx, hipStreamSynchronize(s));
+            for (int64_t j = 0; out_var && j < m; ++j)
+                out_var[r0 + j] = host_kdiag(tp, Xs, ldxs, r0 + j) - quad[(size_t)j];
+        }
+    }
+    if (out_f) HIPCK(ctx, hipMemcpyAsync(out_f, lap + d.f, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    if (out_a) HIPCK(ctx, hipMemcpyAsync(out_a, lap + d.a, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(ctx, hipStreamSynchronize(s));
+    *out_logq = logq;
+    if (out_iters) *out_iters = iters;
+    if (out_converged) *out_converged = converged ? 1 : 0;
+    return 0;
+}
+
 extern "C" {
 
 int gaplac_abi_version(void) { return GAPLAC_ABI_VERSION; }
@@ -3549,6 +3867,92 @@ int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_
     if (out_violations) *out_violations = g.violations;
     if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
     return 0;
+}
+
+int gaplac_laplace_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                          const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
+                          int32_t max_iter, double tol, const double* a0, double* out_logq, double* out_f,
+                          double* out_a, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
+    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0, nullptr, 0,
+                        out_logq, out_f, out_a, nullptr, nullptr, out_iters, out_converged, out_info);
+}
+
+int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                      const gaplac_term* terms, double jitter, int32_t lik, double lik_param,
+                                      const double* y, int32_t max_iter, double tol, const double* a0, int64_t M,
+                                      const double* Xs, int64_t ldxs, double* out_logq, double* out_mean,
+                                      double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
+    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, true, M, Xs, ldxs,
+                        out_logq, nullptr, nullptr, out_mean, out_var, out_iters, out_converged, out_info);
+}
+
+// Host-only walk of the Laplace entries (no device needed): one Newton step with one trial point,
+// the final factorisation, and with M > 0 the posterior query in its chunks, every launch through
+// the functions the entries call. short_ws 1: the workspace and the vectors' buffer one element
+// short.
+int gaplac_plan_check_laplace(int64_t N, int64_t M, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                              int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || M < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 1) return GAPLAC_E_ARG;
+    const LapDims d = lap_dims(N, M);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    double* const fy = reinterpret_cast<double*>((uintptr_t)1 << 46);
+    LaunchGuard gw, gv;  // the workspace (with the vectors and the responses); the vectors alone
+    gw.base = fa;
+    gw.elems = d.a_elems - short_ws;
+    gw.base2 = gv.base = fl;
+    gw.elems2 = gv.elems = d.elems - short_ws;
+    gw.base3 = fy;
+    gw.elems3 = N * d.qc;
+    gw.dry = gv.dry = true;
+    std::vector<LaunchGuard> evals;
+    int rc = 0;
+    auto on = [](LaunchGuard& g, auto&& launches) {
+        GuardScope scope(&g);
+        launches();
+    };
+    auto eval = [&](const ExtraRows& xr) {
+        gaplac_ctx c;
+        c.spw = spw;
+        evals.emplace_back();
+        int e = dry_walk(c, N, xr.on_prebuilt(), evals.back());
+        if (e == GAPLAC_E_ARG && evals.back().violations) e = 0;
+        if (rc == 0) rc = e;
+    };
+    on(gw, [&] { lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl); });
+    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.b, d.c); });
+    on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, true, fa, nullptr, nullptr, nullptr, fl); });
+    eval(ExtraRows{});
+    on(gw, [&] { lap_solve_launches(nullptr, d, N, fa, fl); });
+    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.an, d.fn); });
+    on(gw, [&] {
+        lap_fnew_launches(nullptr, d, N, fl);
+        lap_trial_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, 1.0, nullptr, fl);
+        lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl);
+    });
+    for (int64_t r0 = 0; r0 == 0 || r0 < M; r0 += LAP_CHUNK) {
+        const int64_t m = std::min(LAP_CHUNK, M - r0);
+        if (m > 0) {
+            const int64_t lda = d.Np + NB * ((m + NB - 1) / NB);
+            on(gw, [&] { lap_query_launches(nullptr, d, N, m, lda, fa, nullptr, nullptr, nullptr, nullptr, fl, fy); });
+            eval(ExtraRows::responses(m, nullptr, 0));
+            on(gv, [&] { lap_mf_launches(nullptr, d, N, m, nullptr, nullptr, m, nullptr, fl, d.a, d.mean); });
+        } else {
+            on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, false, fa, nullptr, nullptr, nullptr, fl); });
+            eval(ExtraRows{});
+        }
+    }
+    int64_t launches = gw.launches + gv.launches, violations = gw.violations + gv.violations;
+    std::string first = gw.violations ? gw.first : gv.first;
+    for (const LaunchGuard& g : evals) {
+        launches += g.launches;
+        if (violations == 0 && g.violations) first = g.first;
+        violations += g.violations;
+    }
+    if (out_launches) *out_launches = launches;
+    if (out_violations) *out_violations = violations;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+    return rc;
 }
 
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {

@@ -346,6 +346,29 @@ void launch_fit_rows_solve(hipStream_t s, double* L, int64_t ldl, int nt, int mt
 // and mean in the guarded allocation).
 void launch_fit_mean(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* alpha,
                      const double* Xs, int64_t ldxs, const TermPack* dtp, double* part, double* mean);
+// ---- Laplace approximation ----
+// The matrix lies in the workspace, the guard's first allocation; the vectors (N values each) in one
+// buffer of the context, its second; the test points' response matrix in a third.
+// The likelihood at (a, f), f = K a: g, W, sw = sqrt(W), b = W f + g, and out = {sum log p, a^T f,
+// psi = -a^T f / 2 + sum log p, the count of non-finite W} from per-workgroup partials (lpart:
+// 3 ceil(N / 256) doubles) added in ascending order. y: the observations (unguarded input).
+void launch_laplace_lik(hipStream_t s, int64_t N, int lik, double param, const double* y, const double* a,
+                        const double* f, double* g, double* W, double* sw, double* b, double* lpart, double* out);
+// One trial point of the line search: (at, ft) = (a, f) + step ((an, fn) - (a, f)) and the same sums at it.
+void launch_laplace_trial(hipStream_t s, int64_t N, int lik, double param, double step, const double* y,
+                          const double* a, const double* f, const double* an, const double* fn, double* at, double* ft,
+                          double* lpart, double* out);
+// B = I + diag(sw) K diag(sw) in place over the nt x nt lower tiles of the Gram launch's output in A
+// (ld lda), the right-hand side sw c into row N; the padding stays as gram_tile left it.
+void launch_laplace_b_build(hipStream_t s, double* A, int64_t lda, int64_t N, int nt, const double* sw,
+                            const double* c);
+// y += d x (the diagonal of K that the matrix-free product leaves out).
+void launch_laplace_axpy_diag(hipStream_t s, int64_t N, const double* d, const double* x, double* y);
+// an = b - sw u; u (N values) lies in the workspace, behind the matrix.
+void launch_laplace_anew(hipStream_t s, int64_t N, const double* b, const double* sw, const double* u, double* an);
+// Y (N x M, ld ldy) = diag(sw) K(X, xs): the responses whose transpose rides below B.
+void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* Xs,
+                          int64_t ldxs, const TermPack* dtp, const double* sw, double* Y, int64_t ldy);
 // ---- rand(FiniteGP): out = L z over the factor's lower triangle (partial: ceil(N/512) * N) ----
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,
                      double* out);

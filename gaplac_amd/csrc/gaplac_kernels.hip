@@ -5436,4 +5436,312 @@ void launch_fit_mean(hipStream_t s, int64_t N, int64_t M, const double* X, int64
     fit_mean_finish_kernel<<<dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s>>>(part, M, (int)nk, mean);
 }
 
+// ---------------------------------------------------------------------------------
+// Laplace approximation of a latent GP under a non-Gaussian likelihood (DESIGN.md §10.13;
+// Rasmussen & Williams, Algorithm 3.1). The Newton iteration is the host's (gaplac_api.hip);
+// here: the likelihood's derivatives and sums, the build of B = I + sqrt(W) K sqrt(W) in place
+// over the Gram launch's output, and the elementwise steps around the factorisation.
+// ---------------------------------------------------------------------------------
+
+// log p(y | f), g = d log p / df, W = -d^2 log p / df^2 of one observation.
+__device__ __forceinline__ void lik_eval(int lik, double param, double y, double f, double& lp, double& g,
+                                         double& W) {
+    if (lik == GAPLAC_LIK_BERNOULLI) {
+        // e = exp(-|f|) <= 1: log(1 + e^f) = max(f, 0) + log1p(e), stable in both tails
+        const double e = exp(-fabs(f));
+        const double pi = f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);  // sigma(f)
+        lp = y * f - ((f > 0.0 ? f : 0.0) + log1p(e));
+        g = y - pi;
+        W = e / ((1.0 + e) * (1.0 + e));  // sigma (1 - sigma)
+    } else if (lik == GAPLAC_LIK_POISSON) {
+        const double m = exp(f);
+        lp = y * f - m - lgamma(y + 1.0);
+        g = y - m;
+        W = m;
+    } else {  // GAPLAC_LIK_GAUSSIAN, param = variance
+        const double r = y - f;
+        lp = -0.5 * (1.8378770664093453 + log(param)) - 0.5 * r * r / param;
+        g = r / param;
+        W = 1.0 / param;
+    }
+}
+
+// Sum of three values per thread over the workgroup, fixed tree; the result in thread 0.
+__device__ __forceinline__ void lik_block_sum(double (&v)[3], double (*red)[256]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) red[q][tid] = v[q];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) red[q][tid] += red[q][tid + st];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) v[q] = red[q][0];
+}
+
+// The likelihood at (a, f): g, W, sw = sqrt(W) and b = W f + g per observation, and per
+// workgroup the partial sums of log p, a^T f and the count of non-finite W (an overflowing
+// exp(f)): lpart[q nb + block], q = 0, 1, 2.
+__global__ __launch_bounds__(256) void laplace_lik_kernel(int64_t N, int lik, double param,
+                                                          const double* __restrict__ y, const double* __restrict__ a,
+                                                          const double* __restrict__ f, double* __restrict__ g,
+                                                          double* __restrict__ W, double* __restrict__ sw,
+                                                          double* __restrict__ b, double* __restrict__ lpart) {
+    __shared__ double red[3][256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double v[3] = {0.0, 0.0, 0.0};
+    if (i < N) {
+        const double fi = f[i];
+        double lp, gi, Wi;
+        lik_eval(lik, param, y[i], fi, lp, gi, Wi);
+        g[i] = gi;
+        W[i] = Wi;
+        sw[i] = sqrt(Wi);
+        b[i] = Wi * fi + gi;
+        v[0] = lp;
+        v[1] = a[i] * fi;
+        v[2] = isfinite(Wi) && Wi >= 0.0 ? 0.0 : 1.0;
+    }
+    lik_block_sum(v, red);
+    if (threadIdx.x == 0) {
+        const int64_t nb = gridDim.x;
+        lpart[blockIdx.x] = v[0];
+        lpart[nb + blockIdx.x] = v[1];
+        lpart[2 * nb + blockIdx.x] = v[2];
+    }
+}
+
+// The lighter variant, one trial point of the line search: (at, ft) = (a, f) + s ((an, fn) - (a, f))
+// (s = 1: the Newton point itself, not a rounded copy of it) and the same partial sums at it.
+__global__ __launch_bounds__(256) void laplace_trial_kernel(int64_t N, int lik, double param, double s,
+                                                            const double* __restrict__ y, const double* __restrict__ a,
+                                                            const double* __restrict__ f, const double* __restrict__ an,
+                                                            const double* __restrict__ fn, double* __restrict__ at,
+                                                            double* __restrict__ ft, double* __restrict__ lpart) {
+    __shared__ double red[3][256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double v[3] = {0.0, 0.0, 0.0};
+    if (i < N) {
+        const double ai = s == 1.0 ? an[i] : a[i] + s * (an[i] - a[i]);
+        const double fi = s == 1.0 ? fn[i] : f[i] + s * (fn[i] - f[i]);
+        at[i] = ai;
+        ft[i] = fi;
+        double lp, gi, Wi;
+        lik_eval(lik, param, y[i], fi, lp, gi, Wi);
+        v[0] = lp;
+        v[1] = ai * fi;
+    }
+    lik_block_sum(v, red);
+    if (threadIdx.x == 0) {
+        const int64_t nb = gridDim.x;
+        lpart[blockIdx.x] = v[0];
+        lpart[nb + blockIdx.x] = v[1];
+        lpart[2 * nb + blockIdx.x] = 0.0;
+    }
+}
+
+// The partial sums in ascending block order: out = {sum log p, a^T f, psi = -a^T f / 2 + sum log p,
+// non-finite W count}.
+__global__ __launch_bounds__(64) void laplace_sum_kernel(int nb, const double* __restrict__ lpart,
+                                                         double* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int k = 0; k < nb; ++k) {
+        s0 += lpart[k];
+        s1 += lpart[nb + k];
+        s2 += lpart[2 * nb + k];
+    }
+    out[0] = s0;
+    out[1] = s1;
+    out[2] = -0.5 * s1 + s0;
+    out[3] = s2;
+}
+
+// B = I + diag(sw) K diag(sw) in place over the lower tiles gram_tile wrote (ld lda): one workgroup
+// per 128x128 tile, sw of its rows and columns staged in LDS, each lane two consecutive rows
+// (16-byte loads and stores), each wave every fourth column, eight columns' loads in flight.
+// Entries i, j < N become K_ij (sw_i sw_j) + delta_ij (the product sw_i sw_j commutes, so a
+// diagonal tile stays symmetric); row N of the columns j < N gets the right-hand side sw_j c_j;
+// every padding entry is left as it is (columns j >= N are not touched at all).
+__global__ __launch_bounds__(256) void laplace_b_build_kernel(double* __restrict__ A, int64_t lda, int64_t N,
+                                                              const double* __restrict__ sw,
+                                                              const double* __restrict__ c) {
+    __shared__ double swr[NB], swc[NB], rhs[NB];
+    int bi, bj;
+    tri_index(blockIdx.x, bi, bj);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t r0 = (int64_t)bi * NB, c0 = (int64_t)bj * NB;
+    if (tid < NB) {
+        const int64_t j = c0 + tid;
+        const double s = j < N ? sw[j] : 0.0;
+        swc[tid] = s;
+        rhs[tid] = j < N ? s * c[j] : 0.0;
+    } else {
+        const int64_t i = r0 + tid - NB;
+        swr[tid - NB] = i < N ? sw[i] : 0.0;
+    }
+    __syncthreads();
+    const int64_t i0 = r0 + 2 * lane, i1 = i0 + 1;
+    const double s0 = swr[2 * lane], s1 = swr[2 * lane + 1];
+    double* base = A + c0 * lda + i0;
+    constexpr int U = 8;
+    for (int cb = 0; cb < NB / 4; cb += U) {
+        double2 x[U];
+#pragma unroll
+        for (int q = 0; q < U; ++q) {
+            const int cc = w + 4 * (cb + q);
+            x[q] = make_double2(0.0, 0.0);
+            if (c0 + cc < N && i0 <= N) x[q] = *reinterpret_cast<const double2*>(base + (int64_t)cc * lda);
+        }
+#pragma unroll
+        for (int q = 0; q < U; ++q) {
+            const int cc = w + 4 * (cb + q);
+            const int64_t j = c0 + cc;
+            if (j < N && i0 <= N) {  // (rows beyond N: padding, left alone)
+                const double sj = swc[cc];
+                double2 o = x[q];
+                o.x = i0 < N ? o.x * (s0 * sj) + (i0 == j ? 1.0 : 0.0) : rhs[cc];  // i0 == N: the right-hand side
+                if (i1 < N) o.y = o.y * (s1 * sj) + (i1 == j ? 1.0 : 0.0);
+                else if (i1 == N) o.y = rhs[cc];
+                *reinterpret_cast<double2*>(base + (int64_t)cc * lda) = o;
+            }
+        }
+    }
+}
+
+// y_i += d_i x_i: the diagonal part of K (jitter and the Noise terms) the matrix-free product leaves out.
+__global__ __launch_bounds__(256) void laplace_axpy_diag_kernel(int64_t N, const double* __restrict__ d,
+                                                                const double* __restrict__ x, double* __restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) y[i] += d[i] * x[i];
+}
+
+// a+ = b - sw u (u = B^{-1} (sw c)).
+__global__ __launch_bounds__(256) void laplace_anew_kernel(int64_t N, const double* __restrict__ b,
+                                                           const double* __restrict__ sw, const double* __restrict__ u,
+                                                           double* __restrict__ an) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) an[i] = b[i] - sw[i] * u[i];
+}
+
+// Y[n + j ldy] = sw_n k(xs_j, x_n), n < N, j < M: the test points' scaled cross-covariances as the
+// response matrix whose transpose rides below B (cross_gram_kernel's arithmetic per entry: the
+// latent kernel, a Noise term 0 across point sets). A thread per training point, 64 test points
+// (their coordinates in LDS, read as broadcasts) per workgroup row.
+constexpr int LAP_CROSS_MJ = 64;
+__global__ __launch_bounds__(256) void laplace_cross_kernel(int64_t N, int64_t M, const double* __restrict__ X,
+                                                            int64_t ldx, const double* __restrict__ Xs, int64_t ldxs,
+                                                            const TermPack* __restrict__ tpp,
+                                                            const double* __restrict__ sw, double* __restrict__ Y,
+                                                            int64_t ldy) {
+    __shared__ double xs[GAPLAC_MAX_TERMS][LAP_CROSS_MJ];
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    const int tid = threadIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.y * LAP_CROSS_MJ;
+    for (int idx = tid; idx < T * LAP_CROSS_MJ; idx += 256) {
+        const int t = idx / LAP_CROSS_MJ, jj = idx % LAP_CROSS_MJ;
+        xs[t][jj] = (j0 + jj < M && tp.kind[t] != GAPLAC_NOISE) ? Xs[(int64_t)tp.col[t] * ldxs + j0 + jj] : 0.0;
+    }
+    const int64_t n = (int64_t)blockIdx.x * 256 + tid;
+    double xn[GAPLAC_MAX_TERMS];
+#pragma unroll
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+        xn[t] = 0.0;
+        if (t < T && tp.kind[t] != GAPLAC_NOISE && n < N) xn[t] = X[(int64_t)tp.col[t] * ldx + n];
+    }
+    const double sn = n < N ? sw[n] : 0.0;
+    __syncthreads();
+    if (n >= N) return;
+    const int jn = (int)((M - j0) < LAP_CROSS_MJ ? (M - j0) : LAP_CROSS_MJ);
+    for (int jj = 0; jj < jn; ++jj) {
+        double tot = 0.0, pr = 1.0;
+#pragma unroll
+        for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+            if (t < T) {
+                const int kind = tp.kind[t];
+                pr *= kind == GAPLAC_NOISE ? 0.0 : term_k(kind, tp.p[t], xs[t][jj], xn[t], false);
+                if (tp.last_in_group[t]) {
+                    tot += pr;
+                    pr = 1.0;
+                }
+            }
+        }
+        Y[n + (j0 + jj) * ldy] = sn * tot;
+    }
+}
+
+// Launchers. The vectors live in one buffer of the context (the guard's second allocation), the
+// matrix in its workspace (the first), the response matrix of the test points in a third.
+void launch_laplace_lik(hipStream_t s, int64_t N, int lik, double param, const double* y, const double* a,
+                        const double* f, double* g, double* W, double* sw, double* b, double* lpart, double* out) {
+    if (N <= 0) return;
+    const int64_t nb = (N + 255) / 256;
+    bool ok = guard_launch("laplace_lik_kernel (partials)", lpart, 0, 3 * nb, 1);
+    for (const double* p : {a, f, (const double*)g, (const double*)W, (const double*)sw, (const double*)b})
+        ok = guard_launch("laplace_lik_kernel", p, 0, N, 1) && ok;
+    ok = guard_launch("laplace_sum_kernel", out, 0, 4, 1) && ok;
+    if (!ok) return;
+    laplace_lik_kernel<<<dim3((unsigned)nb), dim3(256), 0, s>>>(N, lik, param, y, a, f, g, W, sw, b, lpart);
+    laplace_sum_kernel<<<dim3(1), dim3(64), 0, s>>>((int)nb, lpart, out);
+}
+
+void launch_laplace_trial(hipStream_t s, int64_t N, int lik, double param, double step, const double* y,
+                          const double* a, const double* f, const double* an, const double* fn, double* at, double* ft,
+                          double* lpart, double* out) {
+    if (N <= 0) return;
+    const int64_t nb = (N + 255) / 256;
+    bool ok = guard_launch("laplace_trial_kernel (partials)", lpart, 0, 3 * nb, 1);
+    for (const double* p : {a, f, an, fn, (const double*)at, (const double*)ft})
+        ok = guard_launch("laplace_trial_kernel", p, 0, N, 1) && ok;
+    ok = guard_launch("laplace_sum_kernel", out, 0, 4, 1) && ok;
+    if (!ok) return;
+    laplace_trial_kernel<<<dim3((unsigned)nb), dim3(256), 0, s>>>(N, lik, param, step, y, a, f, an, fn, at, ft, lpart);
+    laplace_sum_kernel<<<dim3(1), dim3(64), 0, s>>>((int)nb, lpart, out);
+}
+
+void launch_laplace_b_build(hipStream_t s, double* A, int64_t lda, int64_t N, int nt, const double* sw,
+                            const double* c) {
+    if (N <= 0 || nt <= 0) return;
+    bool ok = guard_launch("laplace_b_build_kernel", A, 0, tiles_end(lda, nt - 1, nt - 1));
+    ok = guard_launch("laplace_b_build_kernel (sw)", sw, 0, N, 1) && ok;
+    ok = guard_launch("laplace_b_build_kernel (c)", c, 0, N, 1) && ok;
+    if (!ok) return;
+    const int64_t ntiles = (int64_t)nt * (nt + 1) / 2;
+    laplace_b_build_kernel<<<dim3((unsigned)ntiles), dim3(256), 0, s>>>(A, lda, N, sw, c);
+}
+
+void launch_laplace_axpy_diag(hipStream_t s, int64_t N, const double* d, const double* x, double* y) {
+    if (N <= 0) return;
+    bool ok = guard_launch("laplace_axpy_diag_kernel", y, 0, N, 1);
+    ok = guard_launch("laplace_axpy_diag_kernel (d)", d, 0, N, 1) && ok;
+    ok = guard_launch("laplace_axpy_diag_kernel (x)", x, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_axpy_diag_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(N, d, x, y);
+}
+
+void launch_laplace_anew(hipStream_t s, int64_t N, const double* b, const double* sw, const double* u, double* an) {
+    if (N <= 0) return;
+    bool ok = guard_launch("laplace_anew_kernel", an, 0, N, 1);
+    ok = guard_launch("laplace_anew_kernel (b)", b, 0, N, 1) && ok;
+    ok = guard_launch("laplace_anew_kernel (sw)", sw, 0, N, 1) && ok;
+    ok = guard_launch("laplace_anew_kernel (u)", u, 0, N) && ok;
+    if (!ok) return;
+    laplace_anew_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(N, b, sw, u, an);
+}
+
+void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* Xs,
+                          int64_t ldxs, const TermPack* dtp, const double* sw, double* Y, int64_t ldy) {
+    if (N <= 0 || M <= 0) return;
+    bool ok = guard_launch("laplace_cross_kernel", Y, 0, (M - 1) * ldy + N, 2);
+    ok = guard_launch("laplace_cross_kernel (sw)", sw, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_cross_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)((M + LAP_CROSS_MJ - 1) / LAP_CROSS_MJ)),
+                           dim3(256), 0, s>>>(N, M, X, ldx, Xs, ldxs, dtp, sw, Y, ldy);
+}
+
 }  // namespace gaplac

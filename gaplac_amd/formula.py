@@ -10,6 +10,10 @@
 SURVEY.md Q2): bare `Noise` adds 1.0 * delta_ij by observation index, `Noise(v)` adds
 v * delta_ij.
 
+`Bernoulli` and `Poisson` in the likelihood slot (`y : Poisson ~| ...`, with or without `()`)
+are an extension too: the reference parses the slot, knows only `Gaussian` and then ignores it
+(SURVEY.md Q5). Here they select the Laplace approximation.
+
 The gp part of a formula is Julia expression syntax; the reference `eval`s it inside
 the GaPLAC module (interface.jl:31). Here a small recursive-descent parser accepts the
 same expressions: calls with positional symbols and keyword arguments (`SqExp(:x; l=2)`,
@@ -117,6 +121,26 @@ class Gaussian(AbstractLiklihood):
 
     def __repr__(self):
         return "Gaussian()"
+
+
+class Bernoulli(AbstractLiklihood):
+    """Extension: y in {0, 1} through the logistic link (the Laplace approximation)."""
+
+    def __eq__(self, other):
+        return isinstance(other, Bernoulli)
+
+    def __repr__(self):
+        return "Bernoulli()"
+
+
+class Poisson(AbstractLiklihood):
+    """Extension: counts through the exp link (the Laplace approximation)."""
+
+    def __eq__(self, other):
+        return isinstance(other, Poisson)
+
+    def __repr__(self):
+        return "Poisson()"
 
 
 # --------------------------------------------------------------------------- parser
@@ -311,6 +335,10 @@ def gp_spec(text: str) -> Spec:
             lik = Gaussian()
         elif lik_s in ("Gaussian", "Gaussian()"):
             lik = Gaussian()
+        elif lik_s in ("Bernoulli", "Bernoulli()"):  # (extension, like Noise)
+            lik = Bernoulli()
+        elif lik_s in ("Poisson", "Poisson()"):  # (extension)
+            lik = Poisson()
         else:
             raise UndefVarError(f"UndefVarError: {lik_s} not defined")
     resp = text[:max(spl1, 0)].strip()

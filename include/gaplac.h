@@ -232,6 +232,53 @@ int gaplac_fit_mean(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, 
 int gaplac_fit_mean_var(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs,
                         double* out_mean, double* out_var);
 
+/* Laplace approximation of a latent GP under a non-Gaussian observation model (Rasmussen &
+ * Williams, Algorithms 3.1 and 5.1; ApproximateGPs.jl's LaplaceApproximation). The latent
+ * covariance is K = sum_t K_t(X) + jitter I (the terms' own NOISE stays in K; jitter >= 0 stands
+ * where noise does in the other entries); the likelihood factorises over the observations:
+ *   GAPLAC_LIK_GAUSSIAN   y_i ~ N(f_i, lik_param), lik_param = variance > 0 (the approximation is
+ *                         exact: log q = gaplac_logpdf at noise = jitter + lik_param)
+ *   GAPLAC_LIK_BERNOULLI  logistic link, y_i in {0, 1}: log p = y f - log(1 + e^f)
+ *   GAPLAC_LIK_POISSON    exp link, y_i a non-negative integer value: log p = y f - e^f - lgamma(y+1)
+ * Newton's iteration on psi(a) = -a^T f / 2 + sum_i log p(y_i | f_i), f = K a, from a = a0 (NULL:
+ * 0): per step one factorisation of B = I + sqrt(W) K sqrt(W) (W = -d^2 log p / df^2 >= 0), then the
+ * step (a, f) + s ((a+, f+) - (a, f)) with the first s = 1, 1/2, ... (at most 20 halvings) whose psi
+ * is finite and >= psi_old - tol (1 + |psi_old|). It stops when |psi_new - psi_old| <= tol (1 +
+ * |psi_new|) (*out_converged = 1) or after max_iter steps (*out_converged = 0: not an error; the
+ * results are those of the last iterate). Then W at the last iterate, one more factorisation, and
+ *   log q(y | X) = -a^T f / 2 + sum_i log p(y_i | f_i) - sum_i log L_ii.
+ * out_f / out_a (N values, either may be NULL): the mode f and a = K^{-1} f = grad log p(y | f);
+ * a is a warm start (a0) for a call with nearby parameters. *out_iters: Newton steps taken.
+ * Outputs are NaN-filled first. Returns 0; info > 0 (also in *out_info) when a factorisation of B
+ * failed, which an indefinite matrix cannot cause (B >= I): W was not finite (an overflowing
+ * e^f), the last error's text names B; GAPLAC_E_KIND for an unknown lik; GAPLAC_E_PARAM for
+ * jitter < 0, tol <= 0 or non-finite, max_iter < 1, a Gaussian variance <= 0, or a y outside the
+ * likelihood's support (checked on the host before anything is launched); GAPLAC_E_ARG as the
+ * other entries. N = 0: log q = 0, no steps, converged. The context stays usable after every
+ * failure; two identical calls give bitwise identical results. Not in the reference (its formula's
+ * likelihood slot is parsed and ignored). */
+#define GAPLAC_LIK_GAUSSIAN 0   /* lik_param = variance > 0 */
+#define GAPLAC_LIK_BERNOULLI 1  /* logistic link, y in {0, 1} */
+#define GAPLAC_LIK_POISSON 2    /* exp link, y a non-negative integer value */
+int gaplac_laplace_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                          int32_t T, const gaplac_term* terms, double jitter, int32_t lik,
+                          double lik_param, const double* y, int32_t max_iter, double tol,
+                          const double* a0 /* NULL: 0 */, double* out_logq,
+                          double* out_f /* N, may be NULL */, double* out_a /* N, may be NULL */,
+                          int32_t* out_iters, int32_t* out_converged, int64_t* out_info);
+/* The same iteration, then the latent posterior at M test points (ld ldxs):
+ *   mean_j = sum_n k(xs_j, x_n) a_n,   var_j = k(xs_j, xs_j) - |L^{-1} (sqrt(W) k(X, xs_j))|^2,
+ * the rows sqrt(W_n) k(x_n, xs_j) riding below B in the final factorisation (test points beyond
+ * 4096 in further chunks, each with a factorisation of its own). out_mean / out_var: M values,
+ * either may be NULL. GAPLAC_E_ARG also for M < 0, Xs NULL or ldxs < M. N = 0: the prior (mean 0,
+ * variance kdiag). */
+int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X,
+                                      int64_t ldx, int32_t T, const gaplac_term* terms, double jitter,
+                                      int32_t lik, double lik_param, const double* y, int32_t max_iter,
+                                      double tol, const double* a0, int64_t M, const double* Xs,
+                                      int64_t ldxs, double* out_logq, double* out_mean, double* out_var,
+                                      int32_t* out_iters, int32_t* out_converged, int64_t* out_info);
+
 /* One draw of the FiniteGP: out = L z with C = K(X) + noise I = L L^T
  * and z the N standard-normal values the caller drew (the host keeps the RNG stream, so a
  * given z gives the same sample as the reference). Replaces: rand(rng, FiniteGP(GP(k), X,
@@ -569,6 +616,15 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
  * reference. */
 int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_t short_ws,
                           int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for the Laplace entries: one Newton step (the likelihood, the matrix-free
+ * products, the Gram, the B build, the factorisation of the prebuilt matrix, z, the
+ * back-substitution, the step and one trial point), the final factorisation, and with M > 0 one
+ * posterior query of M points in its chunks (the response matrix, the factorisation with its
+ * riding rows, the matrix-free mean), all against the workspace and the vectors' buffer.
+ * short_ws 1: both one element short (the negative control); 0: as allocated. Not in the
+ * reference. */
+int gaplac_plan_check_laplace(int64_t N, int64_t M, int32_t spw, int32_t short_ws,
+                              int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
 /* The same check for gaplac_sparse_elbo_grad: gaplac_plan_check_sparse at Ms = 0, then the
  * gradient's launches: the order-Mz ones against its scratch, alpha and the product kernel against
  * the first workspace and the scratch. short_ws 1: the first workspace one element short; 2: the

@@ -196,6 +196,20 @@ int main() {
                         ++checks;
                     }
     EXPECT(gaplac_plan_check_fit(10, 0, 1, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "fit: cap = 0 accepted");
+    // the Laplace entries: one Newton step with a trial point, the final factorisation and a
+    // posterior query of M points in its chunks against the workspace and the vectors' buffer;
+    // then both one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t N : {1, 5, 127, 128, 129, 300, 1000, 4096, 10239, 10240, 16384})
+            for (int64_t M : {0, 1, 128, 129, 4096, 4097, 9000})
+                for (int short_ws : {0, 1}) {
+                    const int rc = gaplac_plan_check_laplace(N, M, spw, short_ws, &a, &b, msg, sizeof msg);
+                    EXPECT(rc == 0 && a > 0 && (short_ws ? b >= 1 : b == 0),
+                           "plan_check_laplace N=%lld M=%lld spw=%d short_ws=%d: rc %d violations %lld %s", (long long)N,
+                           (long long)M, spw, short_ws, rc, (long long)b, msg);
+                    ++checks;
+                }
+    EXPECT(gaplac_plan_check_laplace(0, 1, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "laplace: N = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
