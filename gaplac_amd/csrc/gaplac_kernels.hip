@@ -851,6 +851,21 @@ struct Gm {
         __builtin_memcpy(&d, &v, 16);
         return d;
     }
+    // the same loads with the address split as the instruction takes it: a per-lane byte
+    // offset vb (plus a compile-time part the compiler moves into the immediate field) and a
+    // wave-uniform byte offset sb in the scalar operand (tail_update steps only sb in its loop)
+    __device__ __forceinline__ double ldb(uint32_t vb, uint32_t sb) const {
+        const gm_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, vb, sb, AUX);
+        double d;
+        __builtin_memcpy(&d, &v, 8);
+        return d;
+    }
+    __device__ __forceinline__ double2 ld2b(uint32_t vb, uint32_t sb) const {
+        const gm_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, vb, sb, AUX);
+        double2 d;
+        __builtin_memcpy(&d, &v, 16);
+        return d;
+    }
     __device__ __forceinline__ void st(uint32_t i, double d) const {
         gm_u32x2 v;
         __builtin_memcpy(&v, &d, 8);
@@ -3940,8 +3955,22 @@ __device__ __forceinline__ void tail_trsm_pipe(double* smem, unsigned* rowf, dou
 // for a region of RB*32 rows x CB*64
 // columns of tile column j (whole tile: RB = 4, CB = 2; quadrant: RB = 2, CB = 1). 8 waves
 // as 2 (rows) x 4 (columns), each RB x CB blocks of 16x16; fragments straight from global
-// (sc1), two groups of 4 k-steps in flight. P rows start at row0, Q rows at qrow0 (global
+// (sc1), a ring of 8 k-steps in flight. P rows start at row0, Q rows at qrow0 (global
 // rows of the panel), C columns at ccol0 within tile column j's storage.
+// The loop:
+// * Paired rows. Lane fc of the block pair (2p, 2p+1) holds rows 32p + 2fc and 32p + 2fc + 1
+//   of the wave's row span (CB = 2: the Q rows of the column pair likewise), so one 16-byte
+//   access moves both blocks' elements: fragments, the C tile's loads and its sc1 stores.
+//   This relabels which row of the 16x16x4 MFMA is which matrix row; fr still indexes k, so
+//   every C element receives the same products in the same order (bitwise the same result).
+//   It needs even rows of 16-byte-aligned columns (launch_tail checks the matrix; row0,
+//   qrow0 and ccol0 are multiples of 64).
+// * The lane's byte offsets are formed once per task; the k position goes into the loads'
+//   scalar offset operand: no vector address arithmetic in the loop.
+// * k-step t + 8 is requested right behind the MFMAs of k-step t, into the registers they
+//   have just read: every fragment is 8 k-steps ahead of its use and no run of memory
+//   instructions stands between two MFMAs. The prologue fills the ring; the last 8 k-steps
+//   load nothing.
 template <int AUX, int RB, int CB, int KD = 1>
 __device__ __forceinline__ void tail_update(const Gm<AUX>& gC, const Gm<AUX>& gP, int64_t lda, int row0, int ccol0,
                                             int qrow0) {
@@ -3950,52 +3979,80 @@ __device__ __forceinline__ void tail_update(const Gm<AUX>& gC, const Gm<AUX>& gP
     const int wr = wave & 1, wc = wave >> 1;
     const int r0 = row0 + wr * RB * 16, c0 = ccol0 + wc * CB * 16, q0 = qrow0 + wc * CB * 16;
     d4 acc[RB][CB];
+    static_assert(RB % 2 == 0 && (CB == 1 || CB == 2), "row blocks come in pairs");
+    constexpr int RP = RB / 2;     // pairs of row blocks: one 16-byte load feeds both
+    constexpr bool QP = CB == 2;   // the two column blocks' Q rows paired the same way
+    constexpr int NS = KD * NB / 4;  // k-steps
+    constexpr int RING = 8;          // k-steps in flight
+    static_assert(NS % RING == 0 && NS >= 2 * RING, "the ring's fill and drain");
+    // C column of accumulator row fr + 4 rg of column block mj
+    auto ccol = [&](int mj, int rg) { return QP ? c0 + 2 * (fr + 4 * rg) + mj : c0 + fr + 4 * rg; };
 #pragma unroll
-    for (int mi = 0; mi < RB; ++mi)
+    for (int p = 0; p < RP; ++p)
 #pragma unroll
         for (int mj = 0; mj < CB; ++mj)
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg)
-                acc[mi][mj][rg] = gC.ld((uint32_t)((int64_t)(c0 + 16 * mj + fr + 4 * rg) * lda + r0 + 16 * mi + fc));
-    constexpr int G = 4;  // k-steps per group
-    double fa[2][G][CB], fb[2][G][RB];
-    auto load = [&](int buf, int g) {
+            for (int rg = 0; rg < 4; ++rg) {
+                const double2 c = gC.ld2((uint32_t)((int64_t)ccol(mj, rg) * lda + r0 + 32 * p + 2 * fc));
+                acc[2 * p][mj][rg] = c.x;
+                acc[2 * p + 1][mj][rg] = c.y;
+            }
+    double2 fb[RING][RP];
+    double fa[RING][CB];
+    // the lane's part of every fragment address, once per task; the k position is a scalar
+    uint32_t vP = (uint32_t)(((int64_t)fr * lda + r0 + 2 * fc) * 8);
+    uint32_t vQ = (uint32_t)(((int64_t)fr * lda + q0 + (QP ? 2 * fc : fc)) * 8);
+    asm volatile("" : "+v"(vP), "+v"(vQ));  // kept as they are: the loop adds nothing to them
+    const uint32_t kstep = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(4 * lda * 8));
+    auto load = [&](int slot, int t) {  // k-step t into ring slot `slot`
+        const uint32_t sb = kstep * (uint32_t)t;
 #pragma unroll
-        for (int st = 0; st < G; ++st) {
-            const int64_t col = (int64_t)(4 * (G * g + st) + fr) * lda;
-#pragma unroll
-            for (int mi = 0; mi < RB; ++mi) fb[buf][st][mi] = gP.ld((uint32_t)(col + r0 + 16 * mi + fc));
-#pragma unroll
-            for (int mj = 0; mj < CB; ++mj) fa[buf][st][mj] = gP.ld((uint32_t)(col + q0 + 16 * mj + fc));
+        for (int p = 0; p < RP; ++p) fb[slot][p] = gP.ld2b(vP + 256u * p, sb);
+        if (QP) {
+            const double2 a = gP.ld2b(vQ, sb);
+            fa[slot][0] = a.x;
+            fa[slot][CB - 1] = a.y;
+        } else {
+            fa[slot][0] = gP.ldb(vQ, sb);
         }
     };
-    auto compute = [&](int buf) {
+    auto compute = [&](int slot) {
 #pragma unroll
-        for (int st = 0; st < G; ++st)
+        for (int mi = 0; mi < RB; ++mi) {
+            const double b = mi & 1 ? fb[slot][mi >> 1].y : fb[slot][mi >> 1].x;  // negated by the MFMA (neg B)
 #pragma unroll
-            for (int mi = 0; mi < RB; ++mi) {
-                const double b = fb[buf][st][mi];  // negated by the MFMA (neg B)
-#pragma unroll
-                for (int mj = 0; mj < CB; ++mj)
-                    acc[mi][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[buf][st][mj], b, acc[mi][mj], 0, 0, 2);
-            }
+            for (int mj = 0; mj < CB; ++mj)
+                acc[mi][mj] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[slot][mj], b, acc[mi][mj], 0, 0, 2);
+        }
     };
-    constexpr int NG = KD * NB / (4 * G);  // 8 groups per 128 panel columns
-    load(0, 0);
+#pragma unroll
+    for (int s = 0; s < RING; ++s) load(s, s);
 #pragma unroll 1
-    for (int g = 0; g < NG; g += 2) {
-        load(1, g + 1);
-        compute(0);
-        if (g + 2 < NG) load(0, g + 2);
-        compute(1);
+    for (int t0 = 0; t0 < NS - RING; t0 += RING) {
+#pragma unroll
+        for (int s = 0; s < RING; ++s) {
+            compute(s);
+            load(s, t0 + RING + s);
+        }
+#pragma unroll
+        for (int s = 0; s < RING; ++s) {
+            __builtin_amdgcn_sched_group_barrier(0x008, RB * CB, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x020, RP + 1, 0);   // VMEM read
+        }
     }
 #pragma unroll
-    for (int mi = 0; mi < RB; ++mi)
+    for (int s = 0; s < RING; ++s) compute(s);
+#pragma unroll
+    for (int p = 0; p < RP; ++p)
 #pragma unroll
         for (int mj = 0; mj < CB; ++mj)
 #pragma unroll
-            for (int rg = 0; rg < 4; ++rg)
-                gC.st((uint32_t)((int64_t)(c0 + 16 * mj + fr + 4 * rg) * lda + r0 + 16 * mi + fc), acc[mi][mj][rg]);
+            for (int rg = 0; rg < 4; ++rg) {
+                double2 c;
+                c.x = acc[2 * p][mj][rg];
+                c.y = acc[2 * p + 1][mj][rg];
+                gC.st2((uint32_t)((int64_t)ccol(mj, rg) * lda + r0 + 32 * p + 2 * fc), c);
+            }
 }
 
 // (An LDS-staged whole-tile variant of tail_update, panels moved once per workgroup by
@@ -5166,6 +5223,15 @@ void launch_tail(hipStream_t s, const TailArgs& a, int grid, KTime* kt) {
         !guard_launch("tail_kernel", a.A, 0,
                       (int64_t)(a.nmodels - 1) * a.a_stride + tiles_end(a.lda, a.ts + a.T + a.xrows - 1, a.ts + a.T - 1)))
         return;
+    // tail_update moves row pairs with 16-byte accesses: every matrix (the extra rows lie in
+    // the same storage) starts 16-byte aligned and keeps even rows so in every column. Tile
+    // and row-half offsets are multiples of 64. An invariant of the callers' workspaces
+    // (lda a multiple of NB), so a violation is a bug here, not an input error.
+    if (((uintptr_t)a.A & 15u) || (a.lda & 1) || (a.a_stride & 1)) {
+        fprintf(stderr, "gaplac: tail_kernel needs a 16-byte aligned matrix and even lda / stride (A %p, lda %lld, stride %lld)\n",
+                (void*)a.A, (long long)a.lda, (long long)a.a_stride);
+        abort();
+    }
     if (a.gX)
         tail_kernel<true><<<dim3((unsigned)grid), dim3(512), 0, s>>>(a, kt);
     else
