@@ -41,6 +41,7 @@ EXPORTED = (
     "gaplac_fit_mean_var",
     "gaplac_laplace_logpdf",
     "gaplac_laplace_posterior_mean_var",
+    "gaplac_laplace_logpdf_grad",
     "gaplac_rand",
     "gaplac_logpdf_multi",
     "gaplac_logpdf_multi_device",
@@ -67,6 +68,7 @@ EXPORTED = (
     "gaplac_plan_check_joint",
     "gaplac_plan_check_fit",
     "gaplac_plan_check_laplace",
+    "gaplac_plan_check_laplace_grad",
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
     "gaplac_plan_check_sparse_grad_z",
@@ -198,6 +200,10 @@ def load() -> ctypes.CDLL:
     lib.gaplac_laplace_logpdf.argtypes = laplace + [_DP, c_void_p, c_void_p] + status
     lib.gaplac_laplace_posterior_mean_var.argtypes = laplace + [c_int64, c_void_p, c_int64, _DP, c_void_p,
                                                                 c_void_p] + status
+    # (gaplac_laplace_logpdf's arguments, then dparam, djitter and the implicit parts)
+    lib.gaplac_laplace_logpdf_grad.argtypes = laplace + [_DP, c_void_p, c_void_p] + status + [c_void_p, _DP, c_void_p]
+    lib.gaplac_plan_check_laplace_grad.argtypes = [c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64),
+                                                   c_char_p, c_int64]
     lib.gaplac_plan_check_laplace.argtypes = [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64),
                                               c_char_p, c_int64]
     lib.gaplac_rand.argtypes = common + [c_void_p]

@@ -434,6 +434,20 @@ def approx_lml(la: LaplaceApproximation, lfx: LatentFiniteGP, y, ctx: backend.Co
         full=full)
 
 
+def approx_lml_grad(la: LaplaceApproximation, lfx: LatentFiniteGP, y, ctx: backend.Context | None = None, a0=None,
+                    full: bool = False):
+    """(lml, dparam, djitter): approx_lml and its gradient in every term's parameter, in the order of
+    kernels.lower_formula (the order of lfx.fx.terms; l / c / a Noise term's variance, 0 for Cat), and
+    in the jitter (gaplac_laplace_logpdf_grad). For a GaussianLikelihood djitter is also the
+    derivative in its variance. a0: a warm start; full=True returns the backend's LaplaceGradResult."""
+    _gate()
+    y = _laplace_args(la, lfx, y)
+    fx = lfx.fx
+    res = (ctx or backend.default_context()).laplace_logpdf_grad(
+        fx.x, fx.terms, fx.noise, lfx.lik.code, y, lik_param=lfx.lik.param, max_iter=la.maxiter, tol=la.tol, a0=a0)
+    return res if full else (res.logq, res.dparam, res.djitter)
+
+
 class LaplacePosteriorGP:
     """posterior(la, lfx, y): the Gaussian approximation of the latent posterior. The mode is found
     when f_hat (or logq) is first asked for and kept as the warm start of every query; each

@@ -64,6 +64,20 @@ class LaplaceResult:
         return f"LaplaceResult(logq={self.logq!r}, iters={self.iters}, converged={self.converged})"
 
 
+class LaplaceGradResult(LaplaceResult):
+    """What gaplac_laplace_logpdf_grad returns: a LaplaceResult with dparam (one entry per term, in
+    the term's own parameter), djitter, and implicit (T + 1 values: the parts of dparam and djitter
+    that come from the mode's dependence on the parameter)."""
+
+    def __init__(self, logq, f, a, iters, converged, dparam: np.ndarray, djitter: float, implicit: np.ndarray):
+        super().__init__(logq, f, a, iters, converged)
+        self.dparam, self.djitter, self.implicit = dparam, djitter, implicit
+
+    def __repr__(self):
+        return (f"LaplaceGradResult(logq={self.logq!r}, dparam={self.dparam!r}, djitter={self.djitter!r}, "
+                f"iters={self.iters}, converged={self.converged})")
+
+
 class Context:
     """One device, one persistent workspace (gaplac_ctx)."""
 
@@ -267,6 +281,29 @@ class Context:
         if full:
             return LaplaceResult(logq.value, f, a, iters.value, bool(conv.value))
         return logq.value
+
+    def laplace_logpdf_grad(self, X, terms, jitter: float, lik, y, lik_param: float = 0.0, max_iter: int = 100,
+                            tol: float = 1e-12, a0=None) -> LaplaceGradResult:
+        """log q(y | X) of laplace_logpdf and its gradient in every term's parameter (l / c / a Noise
+        term's variance; 0 for Cat) and in the jitter (gaplac_laplace_logpdf_grad): a
+        LaplaceGradResult with .logq .dparam .djitter .implicit .f .a .iters .converged. For the
+        Gaussian likelihood djitter is also the derivative in lik_param. A RuntimeWarning when the
+        iteration did not converge: the gradient is then that of the last iterate, not the exact
+        derivative of the reported log q."""
+        keep, N, _, args = self._laplace_args(X, terms, jitter, lik, y, lik_param, max_iter, tol, a0)
+        T = args[5]
+        logq, dj = c_double(), c_double()
+        f = np.empty(N, dtype=np.float64)
+        a = np.empty(N, dtype=np.float64)
+        dp = np.empty(max(1, T), dtype=np.float64)
+        imp = np.empty(T + 1, dtype=np.float64)
+        iters, conv, info = c_int32(), c_int32(), c_int64()
+        rc = self.lib.gaplac_laplace_logpdf_grad(
+            *args, byref(logq), f.ctypes.data_as(c_void_p), a.ctypes.data_as(c_void_p), byref(iters), byref(conv),
+            byref(info), dp.ctypes.data_as(c_void_p), byref(dj), imp.ctypes.data_as(c_void_p))
+        self._check(rc)
+        self._laplace_warn(bool(conv.value), iters.value)
+        return LaplaceGradResult(logq.value, f, a, iters.value, bool(conv.value), dp[:T].copy(), dj.value, imp)
 
     def laplace_posterior_mean_var(self, X, terms, jitter: float, lik, y, Xs, lik_param: float = 0.0,
                                    max_iter: int = 100, tol: float = 1e-12, a0=None, full: bool = False):

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -48,6 +49,9 @@ struct ExtraRows {
     const double* sub = nullptr;
     bool prebuilt = false;    // the matrix is already in the workspace: no Gram launch (§10.6)
     bool singletons = true;   // mode 1: single-term product groups only (the fused path's case)
+    // mode 1: the evaluation stops after the factorisation; the caller runs the gradient's ending
+    // (enqueue_grad_ending) itself, with its own alpha (the Laplace gradient, §10.14)
+    bool defer_ending = false;
 
     static ExtraRows dense(int mode, int64_t n) {  // n rows in ceil(n / 128) tile rows
         ExtraRows x;
@@ -76,6 +80,11 @@ struct ExtraRows {
         x.Y = Y;
         x.ldy = ldy;
         x.sub = sub;
+        return x;
+    }
+    ExtraRows deferred() const {
+        ExtraRows x = *this;
+        x.defer_ending = true;
         return x;
     }
     // the same rows on a matrix the caller has already put in the workspace
@@ -1109,6 +1118,53 @@ int ensure_tile_lists(gaplac_ctx* ctx, int nt) {
     return 0;
 }
 
+// The gradient's ending after a factorisation with identity rows (Y = L^{-T} below the factor,
+// lda = 2 Np): the contraction of alpha alpha^T - Y Y^T with every dC/dtheta into ctx->gout and
+// its pinned copy. alpha == nullptr (gaplac_logpdf_grad): alpha = Y z from the factor's row N,
+// into ctx->galpha. Else (the Laplace gradient, whose Y is scaled to Y Y^T = R, DESIGN.md
+// §10.14): the caller's vector, final on s_main.
+int enqueue_grad_ending(gaplac_ctx* ctx, int64_t N, int64_t Np, int64_t lda, const double* alpha) {
+    int rc;
+    // Fused (single-term groups): alpha = Y z first (HBM-bound, ~0.2 ms alone), then M =
+    // -C^{-1} tile by tile contracted in place with every dC/dtheta (cinv_contract_kernel:
+    // the tile is never stored nor read back), all on s_main.
+    // Else (or GAPLAC_GRAD_FUSED=0): alpha on s_extra beside M over the factor storage on
+    // s_main (both only read Y; z is copied out first, cinv may overwrite row N), then the
+    // contraction on s_main once alpha is in. Both end in the fixed-order reduction.
+    const bool fused = ctx->grad_fused && ctx->xr.singletons;
+    hipStream_t sm = ctx->s_main;
+    hipStream_t sx = fused || ctx->serial || alpha ? sm : ctx->s_extra;  // alpha's stream
+    const int m = (int)((N + NB - 1) / NB);
+    launch_zero_tail_cols(sm, ctx->A, lda, Np, N);
+    if (!alpha) {
+        launch_copy_z(sm, ctx->A, lda, N, ctx->gz);
+        if (sx != sm) {
+            HIPQ(ctx, hipEventRecord(ctx->ev_xinit, sm));
+            HIPQ(ctx, hipStreamWaitEvent(sx, ctx->ev_xinit, 0));
+        }
+        launch_alpha(sx, ctx->A, lda, Np, N, ctx->gz, ctx->gpart, ctx->galpha, ctx->gdv);
+        if (sx != sm) HIPQ(ctx, hipEventRecord(ctx->ev_xdone, sx));
+        alpha = ctx->galpha;
+    }
+    if ((rc = timed_launch(ctx, ctx->prof_mode == 2, sm, {0, 0.0, 0.0, 8}, [&] {
+             if (fused)
+                 launch_cinv_contract(sm, ctx->A, lda, Np, N, ctx->dX, N, alpha, ctx->dtp, ctx->glist,
+                                      ctx->glist_blocks, ctx->gpart, slot(ctx, 8, 0));
+             else
+                 launch_cinv_tiles(sm, ctx->A, lda, Np, ctx->glist, ctx->glist_blocks, m, slot(ctx, 8, 0));
+         })))
+        return rc;
+    if (!fused) {
+        if (sx != sm) HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
+        launch_grad_contract(sm, ctx->A, lda, N, ctx->dX, N, alpha, ctx->dtp, ctx->dgp, ctx->gpart,
+                             slot(ctx, 9, 0));
+    }
+    launch_grad_reduce(sm, ctx->gpart, m * (m + 1) / 2, ctx->htp->T, ctx->gout);
+    HIPQ(ctx, hipMemcpyAsync(ctx->hgout, ctx->gout, sizeof(double) * (GAPLAC_MAX_TERMS + 1),
+                              hipMemcpyDeviceToHost, sm));
+    return 0;
+}
+
 // Everything one evaluation puts on the streams (eager launch or graph capture): reset
 // the result record (and the profiling slots), Gram build, factorisation schedule,
 // reduction, result copy to the pinned host record. Inputs: ctx->dX (ld N), ctx->dv,
@@ -1161,42 +1217,7 @@ int enqueue_eval_body(gaplac_ctx* ctx, int64_t N, int32_t D, int64_t Np, int nt)
     if (ctx->xr.mode == 3)
         launch_quad_rows(ctx->s_main, ctx->A, lda, Np, N, ctx->xr.M, ctx->dres, ctx->gpart, ctx->mres,
                          ctx->mres ? ctx->mres + ctx->xr.M : nullptr /* (a dry walk has no buffers) */);
-    if (ctx->xr.mode == 1) {
-        // Fused (single-term groups): alpha = Y z first (HBM-bound, ~0.2 ms alone), then M =
-        // -C^{-1} tile by tile contracted in place with every dC/dtheta (cinv_contract_kernel:
-        // the tile is never stored nor read back), all on s_main.
-        // Else (or GAPLAC_GRAD_FUSED=0): alpha on s_extra beside M over the factor storage on
-        // s_main (both only read Y; z is copied out first, cinv may overwrite row N), then the
-        // contraction on s_main once alpha is in. Both end in the fixed-order reduction.
-        const bool fused = ctx->grad_fused && ctx->xr.singletons;
-        hipStream_t sm = ctx->s_main;
-        hipStream_t sx = fused || ctx->serial ? sm : ctx->s_extra;  // alpha's stream
-        const int m = (int)((N + NB - 1) / NB);
-        launch_zero_tail_cols(sm, ctx->A, lda, Np, N);
-        launch_copy_z(sm, ctx->A, lda, N, ctx->gz);
-        if (sx != sm) {
-            HIPQ(ctx, hipEventRecord(ctx->ev_xinit, sm));
-            HIPQ(ctx, hipStreamWaitEvent(sx, ctx->ev_xinit, 0));
-        }
-        launch_alpha(sx, ctx->A, lda, Np, N, ctx->gz, ctx->gpart, ctx->galpha, ctx->gdv);
-        if (sx != sm) HIPQ(ctx, hipEventRecord(ctx->ev_xdone, sx));
-        if ((rc = timed_launch(ctx, ctx->prof_mode == 2, sm, {0, 0.0, 0.0, 8}, [&] {
-                 if (fused)
-                     launch_cinv_contract(sm, ctx->A, lda, Np, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->glist,
-                                          ctx->glist_blocks, ctx->gpart, slot(ctx, 8, 0));
-                 else
-                     launch_cinv_tiles(sm, ctx->A, lda, Np, ctx->glist, ctx->glist_blocks, m, slot(ctx, 8, 0));
-             })))
-            return rc;
-        if (!fused) {
-            if (sx != sm) HIPQ(ctx, hipStreamWaitEvent(sm, ctx->ev_xdone, 0));
-            launch_grad_contract(sm, ctx->A, lda, N, ctx->dX, N, ctx->galpha, ctx->dtp, ctx->dgp, ctx->gpart,
-                                 slot(ctx, 9, 0));
-        }
-        launch_grad_reduce(sm, ctx->gpart, m * (m + 1) / 2, ctx->htp->T, ctx->gout);
-        HIPQ(ctx, hipMemcpyAsync(ctx->hgout, ctx->gout, sizeof(double) * (GAPLAC_MAX_TERMS + 1),
-                                  hipMemcpyDeviceToHost, sm));
-    }
+    if (ctx->xr.mode == 1 && !ctx->xr.defer_ending && (rc = enqueue_grad_ending(ctx, N, Np, lda, nullptr))) return rc;
     HIPQ(ctx, hipMemcpyAsync(ctx->hres, ctx->dres, offsetof(EvalResult, part), hipMemcpyDeviceToHost,
                               ctx->s_main));
     return 0;
@@ -1533,6 +1554,21 @@ int logpdf_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const dou
     return finish(r, out_logpdf, out_logdet, out_quad);
 }
 
+// The product groups' bounds per term (terms validated by pack_terms: groups are contiguous);
+// true when every group is a single term.
+bool pack_groups(int32_t T, const gaplac_term* terms, GradTermPack* gp) {
+    bool singletons = true;
+    for (int t = 0; t < T; ++t) {
+        int a = t, b = t + 1;
+        while (a > 0 && terms[a - 1].group == terms[t].group) --a;
+        while (b < T && terms[b].group == terms[t].group) ++b;
+        gp->gstart[t] = a;
+        gp->gend[t] = b;
+        singletons = singletons && b - a == 1;
+    }
+    return singletons;
+}
+
 // Shared body of gaplac_logpdf_grad / _device.
 int logpdf_grad_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, const double* X, int64_t ldx,
                      int32_t T, const gaplac_term* terms, double noise, const double* v, double* out_logpdf,
@@ -1555,15 +1591,7 @@ int logpdf_grad_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, cons
         return 0;
     }
     GradTermPack gp{};
-    for (int t = 0; t < T; ++t) {
-        int a = t, b = t + 1;
-        while (a > 0 && terms[a - 1].group == terms[t].group) --a;
-        while (b < T && terms[b].group == terms[t].group) ++b;
-        gp.gstart[t] = a;
-        gp.gend[t] = b;
-    }
-    bool singletons = true;
-    for (int t = 0; t < T; ++t) singletons = singletons && gp.gend[t] - gp.gstart[t] == 1;
+    const bool singletons = pack_groups(T, terms, &gp);
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, v, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     tp.noise = noise;
@@ -2221,15 +2249,7 @@ int sparse_elbo_grad_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X
     TermPack tp;
     if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
     GradTermPack gp{};
-    for (int t = 0; t < T; ++t) {
-        int a = t, b = t + 1;
-        while (a > 0 && terms[a - 1].group == terms[t].group) --a;
-        while (b < T && terms[b].group == terms[t].group) ++b;
-        gp.gstart[t] = a;
-        gp.gend[t] = b;
-    }
-    bool groups = false;
-    for (int t = 0; t < T; ++t) groups = groups || gp.gend[t] - gp.gstart[t] > 1;
+    const bool groups = !pack_groups(T, terms, &gp);
     double dsum[GAPLAC_MAX_TERMS + 1] = {};
     host_dkdiag(tp, gp, X, ldx, N, dsum);
     std::vector<double> alpha((size_t)std::max<int64_t>(N, 0));
@@ -2682,7 +2702,9 @@ static int batch_tail_finish(gaplac_ctx* ctx, int p, double* out_logpdf, int64_t
 // behind a fake pointer (never dereferenced: the walk only does pointer arithmetic against
 // the guard's base); the schedule is enqueued dry under g, whose workspace is short_by
 // elements short (the negative control).
-static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& g, int64_t short_by = 0) {
+// after (optional): further launches in the walk's context and under its guard, after the evaluation's.
+static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& g, int64_t short_by = 0,
+                    const std::function<int(gaplac_ctx&)>& after = nullptr) {
     EvalScope scope(&c, xr);
     const int64_t Np = round_up(N + 1, NB);
     const int nt = (int)(Np / NB);
@@ -2709,6 +2731,7 @@ static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& 
     {
         GuardScope gscope(&g);
         rc = enqueue_eval(&c, N, 1, Np, nt);
+        if (rc == 0 && after) rc = after(c);
     }
     c.htp = nullptr;  // nothing of the walk's stays behind in c
     c.A = c.Dinv = nullptr;
@@ -2952,8 +2975,12 @@ struct LapDims {
     int nt;
     int64_t a, f, g, w, sw, b, c, an, fn, diag, part, lpart, out, mean, at, ft, elems;
     int64_t u, a_elems;  // in the workspace
+    // the gradient (§10.14): diag B^{-1}, s2, q = K s2, t = Y^T q, r = Y t, launch_alpha's second
+    // output, the partial sums (the row scaling's, the products' and the bilinear form's), the
+    // implicit parts, and u last (the bilinear form's launch reports a buffer one element short)
+    int64_t dbinv, s2, q, tv, yt, dvs, gpart, gimp, ug;
 };
-static LapDims lap_dims(int64_t N, int64_t M) {
+static LapDims lap_dims(int64_t N, int64_t M, bool grad = false) {
     LapDims d{};
     d.Np = round_up(N + 1, NB);
     d.nt = (int)(d.Np / NB);
@@ -2978,6 +3005,19 @@ static LapDims lap_dims(int64_t N, int64_t M) {
     o += N;
     d.ft = o;
     o += N;
+    if (grad) {  // (M = 0) the final factorisation carries identity rows: lda = 2 Np
+        d.ldq = 2 * d.Np;
+        for (int64_t* p : {&d.dbinv, &d.s2, &d.q, &d.tv, &d.yt, &d.dvs}) {
+            *p = o;
+            o += N;
+        }
+        d.gpart = o;
+        o += std::max(((N + NB - 1) / NB) * N, laplace_grad_bilinear_blocks(N) * (GAPLAC_MAX_TERMS + 1));
+        d.gimp = o;
+        o += GAPLAC_MAX_TERMS + 1;
+        d.ug = o;
+        o += N;
+    }
     d.elems = o;
     d.u = d.ldq * d.Np;
     d.a_elems = d.u + N;
@@ -3030,6 +3070,25 @@ static void lap_query_launches(hipStream_t s, const LapDims& d, int64_t N, int64
     launch_laplace_cross(s, N, m, X, N, Xs, m, dtp, lap + d.sw, Y, N);
 }
 
+// The gradient's stages after the final factorisation with identity rows (ld 2 Np, §10.14).
+// Y's rows scaled by sw with diag B^{-1} on the way, and s2.
+static void lap_grad_scale_launches(hipStream_t s, const LapDims& d, int64_t N, int lik, double* A, double* lap) {
+    launch_laplace_grad_scale(s, A, 2 * d.Np, d.Np, N, lap + d.sw, lap + d.gpart, lap + d.dbinv);
+    launch_laplace_grad_s2(s, N, lik, lap + d.f, lap + d.dbinv, lap + d.s2);
+}
+// q = K s2 finished (its matrix-free part: lap_mf_launches), t = Y^T q, r = Y t, u = s2 - r.
+static void lap_grad_solve_launches(hipStream_t s, const LapDims& d, int64_t N, const double* A, double* lap) {
+    launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.s2, lap + d.q);
+    launch_laplace_grad_tmv(s, A, 2 * d.Np, d.Np, N, lap + d.q, lap + d.gpart, lap + d.tv);
+    launch_alpha(s, A, 2 * d.Np, d.Np, N, lap + d.tv, lap + d.gpart, lap + d.yt, lap + d.dvs);
+    launch_laplace_grad_u(s, N, lap + d.s2, lap + d.yt, lap + d.ug);
+}
+// The implicit part of every parameter and of the jitter.
+static void lap_grad_bilinear_launches(hipStream_t s, const LapDims& d, int64_t N, int T, const double* X,
+                                       const TermPack* dtp, const GradTermPack* dgp, double* lap) {
+    launch_laplace_grad_bilinear(s, N, T, X, N, lap + d.ug, lap + d.a, dtp, dgp, lap + d.gpart, lap + d.gimp);
+}
+
 // The diagonal part of K at training point i that the matrix-free product leaves out: every
 // product group with a NOISE term (0 across point sets), at x_i against itself.
 static double host_noise_diag(const TermPack& tp, const double* X, int64_t ldx, int64_t i) {
@@ -3076,13 +3135,29 @@ static int lap_bad_w(gaplac_ctx* ctx, int64_t N, double count, int64_t* out_info
                            "observations (exp(f) overflows)", (long long)N, count);
 }
 
-// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs) and gaplac_laplace_posterior_mean_var.
+// The outputs of gaplac_laplace_logpdf_grad (each may be NULL).
+struct LapGradOut {
+    double* dparam;    // T
+    double* djitter;
+    double* implicit;  // T + 1
+};
+
+// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs), gaplac_laplace_posterior_mean_var and
+// gaplac_laplace_logpdf_grad (grad: M = 0, the final factorisation carries identity rows).
 static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                         const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
                         int32_t max_iter, double tol, const double* a0, bool posterior, int64_t M, const double* Xs,
                         int64_t ldxs, double* out_logq, double* out_f, double* out_a, double* out_mean,
-                        double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
+                        double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info,
+                        const LapGradOut* grad = nullptr) {
     if (out_logq) *out_logq = NAN;
+    if (grad) {
+        if (grad->djitter) *grad->djitter = NAN;
+        for (int t = 0; t < T && t < GAPLAC_MAX_TERMS; ++t)
+            if (grad->dparam) grad->dparam[t] = NAN;
+        for (int t = 0; t <= T && t <= GAPLAC_MAX_TERMS; ++t)
+            if (grad->implicit) grad->implicit[t] = NAN;
+    }
     if (out_iters) *out_iters = 0;
     if (out_converged) *out_converged = 0;
     if (out_info) *out_info = 0;
@@ -3122,6 +3197,13 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     if (N == 0) {  // no observations: log q = 0 and the prior at the test points
         *out_logq = 0.0;
         if (out_converged) *out_converged = 1;
+        if (grad) {
+            if (grad->djitter) *grad->djitter = 0.0;
+            for (int t = 0; t < T; ++t)
+                if (grad->dparam) grad->dparam[t] = 0.0;
+            for (int t = 0; t <= T; ++t)
+                if (grad->implicit) grad->implicit[t] = 0.0;
+        }
         for (int64_t j = 0; posterior && j < M; ++j) {
             if (out_mean) out_mean[j] = 0.0;
             if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
@@ -3130,7 +3212,7 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     }
     tp.noise = jitter;
     if (!posterior) M = 0;
-    const LapDims d = lap_dims(N, M);
+    const LapDims d = lap_dims(N, M, grad != nullptr);
     if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535)
         return set_err(ctx, GAPLAC_E_OOM, "more than 65535 tile rows in one call");
     HIPCK(ctx, hipSetDevice(ctx->device));
@@ -3143,6 +3225,13 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     const double* const dy = ctx->dv;
     *ctx->htp = tp;
     HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, s));
+    bool singletons = true;
+    if (grad) {  // the product groups' bounds, as gaplac_logpdf_grad packs them
+        GradTermPack gp{};
+        singletons = pack_groups(T, terms, &gp);
+        *ctx->hgp = gp;
+        HIPCK(ctx, hipMemcpyAsync(ctx->dgp, ctx->hgp, sizeof(GradTermPack), hipMemcpyHostToDevice, s));
+    }
     {
         std::vector<double> diag((size_t)N);
         for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = jitter + host_noise_diag(tp, X, ldx, i);
@@ -3223,7 +3312,11 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
                 return rc;
             xr = ExtraRows::responses(m, ctx->dY, N);
         } else {
-            if ((rc = lap_on_ws(ctx, [&] { lap_build_launches(s, d, N, d.Np, false, ctx->A, ctx->dX, dy, ctx->dtp, lap); })))
+            // (the gradient: B in the layout of its identity rows, which leave Y = L^{-T} below it)
+            if (grad) xr = ExtraRows::identity(N, singletons).deferred();
+            if ((rc = lap_on_ws(ctx, [&] {
+                     lap_build_launches(s, d, N, grad ? 2 * d.Np : d.Np, false, ctx->A, ctx->dX, dy, ctx->dtp, lap);
+                 })))
                 return rc;
         }
         if ((rc = eval_device(ctx, N, D, tp, xr.on_prebuilt(), &r))) return rc;
@@ -3240,9 +3333,32 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
                 out_var[r0 + j] = host_kdiag(tp, Xs, ldxs, r0 + j) - quad[(size_t)j];
         }
     }
+    double himp[GAPLAC_MAX_TERMS + 1];
+    if (grad) {
+        // Y's rows times sw (Y Y^T = R) and diag B^{-1}; s2, q = K s2, u = s2 - R q; the explicit part
+        // by the gradient's ending with alpha = a; the implicit part matrix-free
+        EvalScope scope(ctx, ExtraRows::identity(N, singletons));
+        if ((rc = lap_on_ws(ctx, [&] { lap_grad_scale_launches(s, d, N, lik, ctx->A, lap); }))) return rc;
+        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.s2, d.q); })))
+            return rc;
+        if ((rc = lap_on_ws(ctx, [&] { lap_grad_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
+        int erc = 0;
+        if ((rc = lap_on_ws(ctx, [&] { erc = enqueue_grad_ending(ctx, N, d.Np, 2 * d.Np, lap + d.a); }))) return rc;
+        if (erc) return erc;
+        if ((rc = lap_on_ws(ctx, [&] { lap_grad_bilinear_launches(s, d, N, T, ctx->dX, ctx->dtp, ctx->dgp, lap); })))
+            return rc;
+        HIPCK(ctx, hipMemcpyAsync(himp, lap + d.gimp, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
+    }
     if (out_f) HIPCK(ctx, hipMemcpyAsync(out_f, lap + d.f, (size_t)N * 8, hipMemcpyDeviceToHost, s));
     if (out_a) HIPCK(ctx, hipMemcpyAsync(out_a, lap + d.a, (size_t)N * 8, hipMemcpyDeviceToHost, s));
     HIPCK(ctx, hipStreamSynchronize(s));
+    if (grad) {  // explicit (ctx->hgout, copied by the ending) + implicit
+        for (int t = 0; t < T; ++t)
+            if (grad->dparam) grad->dparam[t] = ctx->hgout[t] + himp[t];
+        if (grad->djitter) *grad->djitter = ctx->hgout[T] + himp[T];
+        for (int t = 0; t <= T; ++t)
+            if (grad->implicit) grad->implicit[t] = himp[t];
+    }
     *out_logq = logq;
     if (out_iters) *out_iters = iters;
     if (out_converged) *out_converged = converged ? 1 : 0;
@@ -3884,6 +4000,89 @@ int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, con
                                       double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
     return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, true, M, Xs, ldxs,
                         out_logq, nullptr, nullptr, out_mean, out_var, out_iters, out_converged, out_info);
+}
+
+int gaplac_laplace_logpdf_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                               const gaplac_term* terms, double jitter, int32_t lik, double lik_param,
+                               const double* y, int32_t max_iter, double tol, const double* a0, double* out_logq,
+                               double* out_f, double* out_a, int32_t* out_iters, int32_t* out_converged,
+                               int64_t* out_info, double* out_dparam, double* out_djitter, double* out_implicit) {
+    const LapGradOut g{out_dparam, out_djitter, out_implicit};
+    double logq;
+    const int rc = laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0,
+                                nullptr, 0, &logq, out_f, out_a, nullptr, nullptr, out_iters, out_converged, out_info,
+                                &g);
+    if (out_logq) *out_logq = logq;
+    return rc;
+}
+
+// Host-only walk of gaplac_laplace_logpdf_grad: one Newton step with one trial point, the final
+// factorisation with identity rows and the gradient's stages and ending, every launch through
+// the functions the entry calls. short_ws 1: the workspace one element short; 2: the vectors' buffer.
+int gaplac_plan_check_laplace_grad(int64_t N, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                                   int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
+    const LapDims d = lap_dims(N, 0, true);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    LaunchGuard gw, gv;  // the workspace (with the vectors); the vectors alone
+    gw.base = fa;
+    gw.elems = d.a_elems - (short_ws == 1 ? 1 : 0);
+    gw.base2 = gv.base = fl;
+    gw.elems2 = gv.elems = d.elems - (short_ws == 2 ? 1 : 0);
+    gw.dry = gv.dry = true;
+    std::vector<LaunchGuard> evals;
+    int rc = 0;
+    auto on = [](LaunchGuard& g, auto&& launches) {
+        GuardScope scope(&g);
+        launches();
+    };
+    auto eval = [&](const ExtraRows& xr, const std::function<int(gaplac_ctx&)>& after) {
+        gaplac_ctx c;
+        c.spw = spw;
+        evals.emplace_back();
+        LaunchGuard& g = evals.back();
+        g.base2 = fl;
+        g.elems2 = gw.elems2;
+        int e = dry_walk(c, N, xr.on_prebuilt(), g, 0, after);
+        if (e == GAPLAC_E_ARG && g.violations) e = 0;
+        if (rc == 0) rc = e;
+    };
+    on(gw, [&] { lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl); });
+    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.b, d.c); });
+    on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, true, fa, nullptr, nullptr, nullptr, fl); });
+    eval(ExtraRows{}, nullptr);
+    on(gw, [&] { lap_solve_launches(nullptr, d, N, fa, fl); });
+    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.an, d.fn); });
+    on(gw, [&] {
+        lap_fnew_launches(nullptr, d, N, fl);
+        lap_trial_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, 1.0, nullptr, fl);
+        lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl);
+        lap_build_launches(nullptr, d, N, 2 * d.Np, false, fa, nullptr, nullptr, nullptr, fl);
+    });
+    // the final factorisation; then, in its (dry) context, the gradient's stages: the stages under
+    // the entry's guards, the ending under the walk's own (the workspace of 2 Np x Np elements)
+    // (twice: single-term groups, the fused contraction; product groups, its two-launch form)
+    for (bool singletons : {true, false})
+        eval(ExtraRows::identity(N, singletons).deferred(), [&](gaplac_ctx& c) {
+            on(gw, [&] { lap_grad_scale_launches(nullptr, d, N, GAPLAC_LIK_POISSON, fa, fl); });
+            on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.s2, d.q); });
+            on(gw, [&] { lap_grad_solve_launches(nullptr, d, N, fa, fl); });
+            const int e = enqueue_grad_ending(&c, N, d.Np, 2 * d.Np, fl + d.a);
+            on(gw, [&] { lap_grad_bilinear_launches(nullptr, d, N, 1, nullptr, nullptr, nullptr, fl); });
+            return e;
+        });
+    int64_t launches = gw.launches + gv.launches, violations = gw.violations + gv.violations;
+    std::string first = gw.violations ? gw.first : gv.first;
+    for (const LaunchGuard& g : evals) {
+        launches += g.launches;
+        if (violations == 0 && g.violations) first = g.first;
+        violations += g.violations;
+    }
+    if (out_launches) *out_launches = launches;
+    if (out_violations) *out_violations = violations;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+    return rc;
 }
 
 // Host-only walk of the Laplace entries (no device needed): one Newton step with one trial point,

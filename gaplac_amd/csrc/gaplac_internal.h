@@ -369,6 +369,27 @@ void launch_laplace_anew(hipStream_t s, int64_t N, const double* b, const double
 // Y (N x M, ld ldy) = diag(sw) K(X, xs): the responses whose transpose rides below B.
 void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* Xs,
                           int64_t ldxs, const TermPack* dtp, const double* sw, double* Y, int64_t ldy);
+// ---- gradient of the Laplace log q ----
+// After a factorisation of B with identity rows (lda = 2 Np): row i of Y = L^{-T} times sw_i in
+// place (rows i < N, columns k < N), so that Y Y^T = R = sw B^{-1} sw, and dbinv_i = sum_{k >= i}
+// Y_ik^2 of the unscaled row = diag B^{-1}, per tile column then in ascending order (part:
+// ceil(N / 128) * N doubles).
+void launch_laplace_grad_scale(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t N, const double* sw,
+                               double* part, double* dbinv);
+// out = Y^T q over Y's upper triangle (out_k = sum_{i <= k} Y_ik q_i), per tile row then in
+// ascending order (part as above).
+void launch_laplace_grad_tmv(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, const double* q,
+                             double* part, double* out);
+// s2 = (1 - dbinv) rho / 2, rho = (d^3 log p / df^3) / W of the likelihood at f.
+void launch_laplace_grad_s2(hipStream_t s, int64_t N, int lik, const double* f, const double* dbinv, double* s2);
+// u = s2 - r.
+void launch_laplace_grad_u(hipStream_t s, int64_t N, const double* s2, const double* r, double* u);
+// out[t] = sum_ij u_i dK_ij/dtheta_t a_j, t < T, and out[T] = sum_i u_i a_i, matrix-free
+// (partial: laplace_grad_bilinear_blocks(N) * (T + 1) doubles), fixed order.
+int64_t laplace_grad_bilinear_blocks(int64_t N);
+void launch_laplace_grad_bilinear(hipStream_t s, int64_t N, int T, const double* X, int64_t ldx, const double* u,
+                                  const double* a, const TermPack* dtp, const GradTermPack* dgp, double* partial,
+                                  double* out);
 // ---- rand(FiniteGP): out = L z over the factor's lower triangle (partial: ceil(N/512) * N) ----
 void launch_lower_mv(hipStream_t s, const double* A, int64_t lda, int64_t N, const double* z, double* partial,
                      double* out);

@@ -5810,4 +5810,284 @@ void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, 
                            dim3(256), 0, s>>>(N, M, X, ldx, Xs, ldxs, dtp, sw, Y, ldy);
 }
 
+// ---------------------------------------------------------------------------------
+// Gradient of the Laplace log q in the kernel parameters and the jitter (DESIGN.md §10.14;
+// Rasmussen & Williams, Algorithm 5.1). B is factored with identity rows, so Y = L^{-T} (upper
+// triangular, tile (E, J) at A + J NB lda + Np + E NB) lies below the factor. One pass scales
+// its row i by sw_i and sums the squares of the unscaled row (diag B^{-1}); then Y Y^T =
+// R = sw B^{-1} sw, which the gradient's contraction kernels take in the place of C^{-1}. The
+// implicit part needs two products by R (one with Y^T, one with Y) and one matrix-free
+// bilinear form per parameter.
+// ---------------------------------------------------------------------------------
+
+// One workgroup per upper tile (E, J), E <= J: each lane two consecutive rows (16-byte loads and
+// stores), each wave every fourth column in ascending order, eight columns' loads in flight.
+// Rows i < N of the columns k < N are multiplied by sw_i in place (the entries below the
+// diagonal of a diagonal tile too: they are zero or never read); part[J N + i] = the sum of the
+// unscaled squares over the tile's columns k >= i, the waves' sums added in ascending order.
+__global__ __launch_bounds__(256) void laplace_grad_scale_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                                 int64_t N, const double* __restrict__ sw,
+                                                                 double* __restrict__ part) {
+    __shared__ double red[4][NB];
+    int J, E;
+    tri_index(blockIdx.x, J, E);  // J >= E
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t i0 = (int64_t)E * NB + 2 * lane, i1 = i0 + 1, c0 = (int64_t)J * NB;
+    const double s0 = i0 < N ? sw[i0] : 0.0, s1 = i1 < N ? sw[i1] : 0.0;
+    double* base = A + c0 * lda + Np + i0;
+    double q0 = 0.0, q1 = 0.0;
+    constexpr int U = 8;
+    for (int cb = 0; cb < NB / 4; cb += U) {
+        double2 x[U];
+#pragma unroll
+        for (int q = 0; q < U; ++q) {
+            const int cc = w + 4 * (cb + q);
+            x[q] = make_double2(0.0, 0.0);
+            if (c0 + cc < N && i0 < N) x[q] = *reinterpret_cast<const double2*>(base + (int64_t)cc * lda);
+        }
+#pragma unroll
+        for (int q = 0; q < U; ++q) {
+#pragma clang fp contract(off)
+            const int cc = w + 4 * (cb + q);
+            const int64_t k = c0 + cc;
+            if (k < N && i0 < N) {
+                double2 o = x[q];
+                if (k >= i0) q0 += o.x * o.x;
+                if (k >= i1 && i1 < N) q1 += o.y * o.y;
+                o.x *= s0;
+                if (i1 < N) o.y *= s1;  // (i1 == N: a padding row of Y, stored back as read)
+                *reinterpret_cast<double2*>(base + (int64_t)cc * lda) = o;
+            }
+        }
+    }
+    red[w][2 * lane] = q0;
+    red[w][2 * lane + 1] = q1;
+    __syncthreads();
+    if (tid < NB) {
+        const int64_t i = (int64_t)E * NB + tid;
+        if (i < N) part[(int64_t)J * N + i] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// t = Y^T q over the upper triangle, partial sums: workgroup (E, J), E <= J, its 128 rows' share of
+// the columns' dot products. A wave takes every fourth column; its lanes hold two consecutive
+// rows each (q in registers), the products are added by the wave's butterfly (the same order in
+// every call): part[E N + k], k < N.
+__global__ __launch_bounds__(256) void laplace_grad_tmv_kernel(const double* __restrict__ A, int64_t lda, int64_t Np,
+                                                               int64_t N, const double* __restrict__ q,
+                                                               double* __restrict__ part) {
+    int J, E;
+    tri_index(blockIdx.x, J, E);  // J >= E
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t i0 = (int64_t)E * NB + 2 * lane, i1 = i0 + 1, c0 = (int64_t)J * NB;
+    const double qa = i0 < N ? q[i0] : 0.0, qb = i1 < N ? q[i1] : 0.0;
+    const double* base = A + c0 * lda + Np + i0;
+    constexpr int U = 8;
+    for (int cb = 0; cb < NB / 4; cb += U) {
+        double2 x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int cc = w + 4 * (cb + u);
+            x[u] = make_double2(0.0, 0.0);
+            if (c0 + cc < N && i0 < N) x[u] = *reinterpret_cast<const double2*>(base + (int64_t)cc * lda);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma clang fp contract(off)
+            const int cc = w + 4 * (cb + u);
+            const int64_t k = c0 + cc;
+            if (k >= N) continue;  // (uniform in the wave)
+            const double a = (i0 < N && i0 <= k) ? x[u].x * qa : 0.0;
+            const double b = (i1 < N && i1 <= k) ? x[u].y * qb : 0.0;
+            const double sum = wave_sum(a + b);
+            if (lane == 0) part[(int64_t)E * N + k] = sum;
+        }
+    }
+}
+
+// out_i = the chunks' partial sums part[c N + i] in ascending order: upper, c = i / 128 .. m - 1
+// (the row sums of laplace_grad_scale_kernel); else c = 0 .. i / 128 (the column sums of
+// laplace_grad_tmv_kernel).
+__global__ __launch_bounds__(256) void laplace_grad_colsum_kernel(const double* __restrict__ part, int64_t N, int m,
+                                                                  int upper, double* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int t = (int)(i / NB);
+    const int lo = upper ? t : 0, hi = upper ? m - 1 : t;
+    double s = 0.0;
+    for (int c = lo; c <= hi; ++c) s += part[(int64_t)c * N + i];
+    out[i] = s;
+}
+
+// s2_i = (1 - diag B^{-1}_i) rho_i / 2 with rho = (d^3 log p / df^3) / W: tanh(f / 2) (Bernoulli,
+// = 2 sigma(f) - 1), -1 (Poisson), 0 (Gaussian). Nothing is divided by W.
+__global__ __launch_bounds__(256) void laplace_grad_s2_kernel(int64_t N, int lik, const double* __restrict__ f,
+                                                              const double* __restrict__ dbinv,
+                                                              double* __restrict__ s2) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const double rho = lik == GAPLAC_LIK_BERNOULLI ? tanh(0.5 * f[i]) : lik == GAPLAC_LIK_POISSON ? -1.0 : 0.0;
+    s2[i] = 0.5 * (1.0 - dbinv[i]) * rho;
+}
+
+// u = s2 - r (r = R K s2).
+__global__ __launch_bounds__(256) void laplace_grad_u_kernel(int64_t N, const double* __restrict__ s2,
+                                                             const double* __restrict__ r, double* __restrict__ u) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < N) u[i] = s2[i] - r[i];
+}
+
+// The implicit part, matrix-free: partial[block (T + 1) + t] = the block's share of sum_ij u_i
+// dK_ij/dtheta_t a_j (t < T; term_dk, inside a product group times the group's other terms, as
+// grad_contract_kernel forms it) and of sum_i u_i a_i (t = T: the jitter). fit_mean_partial_kernel's
+// tiling: workgroup (x, y) = rows 64 x .. 64 x + 63, one per lane and the same in all four waves,
+// against the columns of chunk y (their coordinates and a staged in LDS, read as broadcasts), a
+// quarter of the chunk per wave in ascending order; then the wave's butterfly and the four waves
+// in ascending order.
+__global__ __launch_bounds__(256) void laplace_grad_bilinear_kernel(int64_t N, const double* __restrict__ X,
+                                                                    int64_t ldx, const double* __restrict__ u,
+                                                                    const double* __restrict__ a,
+                                                                    const TermPack* __restrict__ tpp,
+                                                                    const GradTermPack* __restrict__ gpp,
+                                                                    double* __restrict__ partial) {
+#pragma clang fp contract(off)
+    __shared__ double xcol[GAPLAC_MAX_TERMS][FIT_MEAN_NC];
+    __shared__ double as[FIT_MEAN_NC];
+    __shared__ double red[4][GAPLAC_MAX_TERMS + 1];
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t n0 = (int64_t)blockIdx.y * FIT_MEAN_NC;
+    for (int idx = tid; idx < T * FIT_MEAN_NC; idx += 256) {
+        const int t = idx / FIT_MEAN_NC, cc = idx % FIT_MEAN_NC;
+        xcol[t][cc] = (n0 + cc < N && tp.kind[t] != GAPLAC_NOISE) ? X[(int64_t)tp.col[t] * ldx + n0 + cc] : 0.0;
+    }
+    as[tid] = n0 + tid < N ? a[n0 + tid] : 0.0;
+    const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+    double xa[GAPLAC_MAX_TERMS];
+#pragma unroll
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+        xa[t] = 0.0;
+        if (t < T && tp.kind[t] != GAPLAC_NOISE && i < N) xa[t] = X[(int64_t)tp.col[t] * ldx + i];
+    }
+    const double ui = i < N ? u[i] : 0.0;
+    double g[GAPLAC_MAX_TERMS + 1];
+#pragma unroll
+    for (int t = 0; t <= GAPLAC_MAX_TERMS; ++t) g[t] = 0.0;
+    __syncthreads();
+    const int kn = (int)((N - n0) < FIT_MEAN_NC ? (N - n0) : FIT_MEAN_NC);
+    const int ce = (64 * w + 64) < kn ? (64 * w + 64) : kn;
+    for (int cc = 64 * w; cc < ce; ++cc) {
+        const bool diag = i == n0 + cc;
+        const double ua = ui * as[cc];
+        if (diag) g[GAPLAC_MAX_TERMS] += ua;
+#pragma unroll
+        for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+            if (t < T) {
+                double d = term_dk(tp.kind[t], tp.p[t], xa[t], xcol[t][cc], diag);
+                const int gs = gpp->gstart[t], ge = gpp->gend[t];
+                if (ge - gs > 1) {
+#pragma unroll
+                    for (int s2 = 0; s2 < GAPLAC_MAX_TERMS; ++s2)
+                        if (s2 >= gs && s2 < ge && s2 != t)
+                            d *= term_k(tp.kind[s2], tp.p[s2], xa[s2], xcol[s2][cc], diag);
+                }
+                g[t] += ua * d;
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t <= GAPLAC_MAX_TERMS; ++t) {
+        const double x = wave_sum(g[t]);
+        if (lane == 0) red[w][t] = x;
+    }
+    __syncthreads();
+    if (tid <= T) {
+        const int t = tid == T ? GAPLAC_MAX_TERMS : tid;
+        const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        partial[b * (T + 1) + tid] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    }
+}
+
+// out[t] = sum_b partial[b (T + 1) + t], t = 0..T: grad_reduce_kernel's order, without its 1/2.
+__global__ __launch_bounds__(256) void laplace_grad_sum_kernel(const double* __restrict__ partial, int64_t nb, int T,
+                                                               double* __restrict__ out) {
+    __shared__ double s[256];
+    const int t = blockIdx.x, tid = threadIdx.x;
+    double x = 0.0;
+    for (int64_t b = tid; b < nb; b += 256) x += partial[b * (T + 1) + t];
+    s[tid] = x;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s[tid] += s[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) out[t] = s[0];
+}
+
+// Launchers: Y in the workspace (the guard's first allocation), every vector and partial sum in
+// the context's Laplace buffer (its second).
+void launch_laplace_grad_scale(hipStream_t s, double* A, int64_t lda, int64_t Np, int64_t N, const double* sw,
+                               double* part, double* dbinv) {
+    if (N <= 0) return;
+    const int64_t m = (N + NB - 1) / NB;
+    // (a lane's second row may be row N: read and stored back as it is)
+    bool ok = guard_launch("laplace_grad_scale_kernel", A, Np, (N - 1) * lda + Np + N + 1);
+    ok = guard_launch("laplace_grad_scale_kernel (sw)", sw, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_scale_kernel (partials)", part, 0, m * N, 1) && ok;
+    ok = guard_launch("laplace_grad_colsum_kernel", dbinv, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_grad_scale_kernel<<<dim3((unsigned)(m * (m + 1) / 2)), dim3(256), 0, s>>>(A, lda, Np, N, sw, part);
+    laplace_grad_colsum_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(part, N, (int)m, 1, dbinv);
+}
+
+void launch_laplace_grad_tmv(hipStream_t s, const double* A, int64_t lda, int64_t Np, int64_t N, const double* q,
+                             double* part, double* out) {
+    if (N <= 0) return;
+    const int64_t m = (N + NB - 1) / NB;
+    bool ok = guard_launch("laplace_grad_tmv_kernel", A, Np, (N - 1) * lda + Np + N + 1);
+    ok = guard_launch("laplace_grad_tmv_kernel (q)", q, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_tmv_kernel (partials)", part, 0, m * N, 1) && ok;
+    ok = guard_launch("laplace_grad_colsum_kernel", out, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_grad_tmv_kernel<<<dim3((unsigned)(m * (m + 1) / 2)), dim3(256), 0, s>>>(A, lda, Np, N, q, part);
+    laplace_grad_colsum_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(part, N, (int)m, 0, out);
+}
+
+void launch_laplace_grad_s2(hipStream_t s, int64_t N, int lik, const double* f, const double* dbinv, double* s2) {
+    if (N <= 0) return;
+    bool ok = guard_launch("laplace_grad_s2_kernel", s2, 0, N, 1);
+    ok = guard_launch("laplace_grad_s2_kernel (f)", f, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_s2_kernel (diag)", dbinv, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_grad_s2_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(N, lik, f, dbinv, s2);
+}
+
+void launch_laplace_grad_u(hipStream_t s, int64_t N, const double* s2, const double* r, double* u) {
+    if (N <= 0) return;
+    bool ok = guard_launch("laplace_grad_u_kernel", u, 0, N, 1);
+    ok = guard_launch("laplace_grad_u_kernel (s2)", s2, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_u_kernel (r)", r, 0, N, 1) && ok;
+    if (!ok) return;
+    laplace_grad_u_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(N, s2, r, u);
+}
+
+int64_t laplace_grad_bilinear_blocks(int64_t N) { return ((N + 63) / 64) * ((N + FIT_MEAN_NC - 1) / FIT_MEAN_NC); }
+
+void launch_laplace_grad_bilinear(hipStream_t s, int64_t N, int T, const double* X, int64_t ldx, const double* u,
+                                  const double* a, const TermPack* dtp, const GradTermPack* dgp, double* partial,
+                                  double* out) {
+    if (N <= 0) return;
+    const int64_t bx = (N + 63) / 64, by = (N + FIT_MEAN_NC - 1) / FIT_MEAN_NC;
+    bool ok = guard_launch("laplace_grad_bilinear_kernel", partial, 0, bx * by * (T + 1), 1);
+    ok = guard_launch("laplace_grad_bilinear_kernel (u)", u, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_bilinear_kernel (a)", a, 0, N, 1) && ok;
+    ok = guard_launch("laplace_grad_sum_kernel", out, 0, T + 1, 1) && ok;
+    if (!ok) return;
+    laplace_grad_bilinear_kernel<<<dim3((unsigned)bx, (unsigned)by), dim3(256), 0, s>>>(N, X, ldx, u, a, dtp, dgp,
+                                                                                       partial);
+    laplace_grad_sum_kernel<<<dim3((unsigned)(T + 1)), dim3(256), 0, s>>>(partial, bx * by, T, out);
+}
+
 }  // namespace gaplac

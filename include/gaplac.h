@@ -278,6 +278,34 @@ int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, con
                                       double tol, const double* a0, int64_t M, const double* Xs,
                                       int64_t ldxs, double* out_logq, double* out_mean, double* out_var,
                                       int32_t* out_iters, int32_t* out_converged, int64_t* out_info);
+/* The same iteration (f, a, iters and converged come out bitwise equal to gaplac_laplace_logpdf's),
+ * then the gradient of log q in every term's parameter and in the jitter (Rasmussen & Williams,
+ * Algorithm 5.1). With K~ = K + jitter I, R = sqrt(W) B^{-1} sqrt(W), rho_i = (d^3 log p / df_i^3) /
+ * W_i (Bernoulli: tanh(f_i / 2); Poisson: -1; Gaussian: 0; nothing is divided by W):
+ *   s2 = (1 - diag B^{-1}) rho / 2,   u = s2 - R (K~ s2),
+ *   d log q / d theta_t = 1/2 sum_ij (a_i a_j - R_ij) dK~_ij/dtheta_t + sum_ij u_i dK~_ij/dtheta_t a_j,
+ *   d log q / d jitter  = 1/2 (a^T a - tr R) + u^T a.
+ * The first sums are the explicit part (the mode held fixed), the second the implicit part (the
+ * mode moves with the parameter). The final factorisation of B carries identity rows, which leave
+ * L^{-T}; its rows scaled by sqrt(W) give R as a product, and gaplac_logpdf_grad's contraction runs
+ * on it with alpha = a. out_dparam[t]: explicit + implicit, in the term's own parameter (l, c or a
+ * Noise term's variance; 0 for Cat), inside a product group times the group's other terms.
+ * *out_djitter likewise; for the Gaussian likelihood d log q / d lik_param equals *out_djitter
+ * (log q depends on jitter + lik_param alone). out_implicit (T + 1 values): the implicit parts of
+ * dparam and djitter alone (exactly 0 for the Gaussian likelihood). Every output pointer may be
+ * NULL; all are NaN-filled first. Return codes, *out_info and the context's state after a failure as
+ * gaplac_laplace_logpdf; N = 0: log q = 0 and every gradient 0. Not converged (*out_converged = 0)
+ * is not an error: the gradient is then the same expression at the last iterate, which is not the
+ * exact derivative of the reported log q (the expression assumes a stationary point). Two
+ * identical calls give bitwise identical results. Not in the reference. */
+int gaplac_laplace_logpdf_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                               int32_t T, const gaplac_term* terms, double jitter, int32_t lik,
+                               double lik_param, const double* y, int32_t max_iter, double tol,
+                               const double* a0 /* NULL: 0 */, double* out_logq,
+                               double* out_f /* N */, double* out_a /* N */, int32_t* out_iters,
+                               int32_t* out_converged, int64_t* out_info, double* out_dparam /* T */,
+                               double* out_djitter,
+                               double* out_implicit /* T + 1: the implicit parts of dparam and djitter, may be NULL */);
 
 /* One draw of the FiniteGP: out = L z with C = K(X) + noise I = L L^T
  * and z the N standard-normal values the caller drew (the host keeps the RNG stream, so a
@@ -625,6 +653,14 @@ int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_
  * reference. */
 int gaplac_plan_check_laplace(int64_t N, int64_t M, int32_t spw, int32_t short_ws,
                               int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for gaplac_laplace_logpdf_grad: one Newton step as above, the final factorisation
+ * of B with identity rows, and the gradient's launches (the row scaling with diag B^{-1}, s2, the
+ * matrix-free product, the two products by Y, gaplac_logpdf_grad's ending with alpha = a, the
+ * bilinear form), against the workspace and the vectors' buffer. short_ws 1: the workspace one
+ * element short; 2: the vectors' buffer (the negative controls); 0: as allocated. Not in the
+ * reference. */
+int gaplac_plan_check_laplace_grad(int64_t N, int32_t spw, int32_t short_ws, int64_t* out_launches,
+                                   int64_t* out_violations, char* msg, int64_t msglen);
 /* The same check for gaplac_sparse_elbo_grad: gaplac_plan_check_sparse at Ms = 0, then the
  * gradient's launches: the order-Mz ones against its scratch, alpha and the product kernel against
  * the first workspace and the scratch. short_ws 1: the first workspace one element short; 2: the

@@ -210,6 +210,19 @@ int main() {
                     ++checks;
                 }
     EXPECT(gaplac_plan_check_laplace(0, 1, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG, "laplace: N = 0 accepted");
+    // the Laplace gradient: the Newton step, the final factorisation with identity rows, the
+    // gradient's stages and ending; then the workspace (1) and the vectors' buffer (2) one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t N : {1, 5, 127, 128, 129, 300, 1000, 2049, 3400, 4096, 10239, 10240, 16384})
+            for (int short_ws : {0, 1, 2}) {
+                const int rc = gaplac_plan_check_laplace_grad(N, spw, short_ws, &a, &b, msg, sizeof msg);
+                EXPECT(rc == 0 && a > 0 && (short_ws ? b >= 1 : b == 0),
+                       "plan_check_laplace_grad N=%lld spw=%d short_ws=%d: rc %d violations %lld %s", (long long)N, spw,
+                       short_ws, rc, (long long)b, msg);
+                ++checks;
+            }
+    EXPECT(gaplac_plan_check_laplace_grad(0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG,
+           "laplace gradient: N = 0 accepted");
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
