@@ -39,6 +39,12 @@ EXPORTED = (
     "gaplac_fit_alpha",
     "gaplac_fit_mean",
     "gaplac_fit_mean_var",
+    "gaplac_fit_mean_cov",
+    "gaplac_fit_mode",
+    "gaplac_fit_laplace_info",
+    "gaplac_laplace_fit_create",
+    "gaplac_gauss_hermite",
+    "gaplac_laplace_predict",
     "gaplac_laplace_logpdf",
     "gaplac_laplace_posterior_mean_var",
     "gaplac_laplace_logpdf_grad",
@@ -69,6 +75,7 @@ EXPORTED = (
     "gaplac_plan_check_fit",
     "gaplac_plan_check_laplace",
     "gaplac_plan_check_laplace_grad",
+    "gaplac_plan_check_laplace_fit",
     "gaplac_plan_check_sparse",
     "gaplac_plan_check_sparse_grad",
     "gaplac_plan_check_sparse_grad_z",
@@ -202,6 +209,16 @@ def load() -> ctypes.CDLL:
                                                                 c_void_p] + status
     # (gaplac_laplace_logpdf's arguments, then dparam, djitter and the implicit parts)
     lib.gaplac_laplace_logpdf_grad.argtypes = laplace + [_DP, c_void_p, c_void_p] + status + [c_void_p, _DP, c_void_p]
+    # (the fitted Laplace posterior: gaplac_laplace_logpdf's head, then cap and the handle's address)
+    lib.gaplac_laplace_fit_create.argtypes = laplace + [c_int64, POINTER(c_void_p)] + status
+    lib.gaplac_fit_mode.argtypes = [c_void_p, c_void_p]
+    lib.gaplac_fit_laplace_info.argtypes = [c_void_p, POINTER(c_int32), _DP, _DP, POINTER(c_int32), POINTER(c_int32)]
+    lib.gaplac_fit_mean_cov.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_int64]
+    lib.gaplac_gauss_hermite.argtypes = [c_int32, c_void_p, c_void_p]
+    lib.gaplac_laplace_predict.argtypes = [c_int32, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_void_p, c_void_p, c_void_p]
+    lib.gaplac_plan_check_laplace_fit.argtypes = [c_int64, c_int64, c_int64, c_int32, c_int32, POINTER(c_int64),
+                                                  POINTER(c_int64), c_char_p, c_int64]
     lib.gaplac_plan_check_laplace_grad.argtypes = [c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64),
                                                    c_char_p, c_int64]
     lib.gaplac_plan_check_laplace.argtypes = [c_int64, c_int64, c_int32, c_int32, POINTER(c_int64), POINTER(c_int64),

@@ -493,6 +493,74 @@ class LaplacePosteriorGP:
     def var(self, x):
         return self.mean_and_var(x)[1]
 
+    def fit(self, cap: int = 1024):
+        """The mode found once and the factor of B kept on the device (gaplac_laplace_fit_create):
+        a FittedLaplacePosteriorGP whose queries take neither Newton steps nor a factorisation.
+        cap: the test points solved at once (larger queries run in chunks)."""
+        _gate()
+        fx, lik = self.prior, self.lfx.lik
+        a0 = self._res.a if self._res is not None and self._res.converged else None
+        return FittedLaplacePosteriorGP(self, self._ctx().laplace_fit(
+            fx.x, fx.terms, fx.noise, lik.code, self.y, lik_param=lik.param, max_iter=self.la.maxiter,
+            tol=self.la.tol, a0=a0, cap=cap))
+
+
+class FittedLaplacePosteriorGP:
+    """LaplacePosteriorGP.fit(): the same latent posterior behind a kept factorisation of B
+    (backend.Fit of kind "laplace"). mean_and_var and var solve the test rows against the kept
+    factor, mean alone is the matrix-free K(xs, X) a, mean_and_cov the joint covariance of at most
+    cap points, predict the observation-space summaries. Close it (or use it as a context manager)
+    to free the device memory early."""
+
+    def __init__(self, f: LaplacePosteriorGP, fit: "backend.Fit"):
+        self.f = f
+        self.prior = f.prior
+        self.y = f.y
+        self.handle = fit
+
+    @staticmethod
+    def _xs(x):
+        X = np.asarray(x, dtype=np.float64)
+        return X[:, None] if X.ndim == 1 else X
+
+    @property
+    def f_hat(self):
+        """The mode of the latent posterior at the training inputs."""
+        return self.handle.f_hat()
+
+    @property
+    def logq(self):
+        return self.handle.logq
+
+    def mean_and_var(self, x):
+        _gate()
+        return self.handle.mean_var(self._xs(x))
+
+    def mean(self, x):
+        _gate()
+        return self.handle.mean(self._xs(x))
+
+    def var(self, x):
+        return self.mean_and_var(x)[1]
+
+    def mean_and_cov(self, x, noise=0.0):
+        _gate()
+        return self.handle.mean_cov(self._xs(x), noise_s=noise)
+
+    def predict(self, x, ys=None, Q: int = 32):
+        """(ymean, yvar[, logp]) of the observations at the rows of x under the likelihood."""
+        _gate()
+        return self.handle.predict(self._xs(x), ys=ys, Q=Q)
+
+    def close(self):
+        self.handle.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
 
 def posterior(*args, ctx: backend.Context | None = None):
     """AbstractGPs.posterior(fx, y) (CLI/src/select.jl:51-52, src/plotting.jl:8), or

@@ -343,6 +343,21 @@ class Context:
             y.ctypes.data_as(c_void_p), int(cap), byref(h),
         )
         self._check(rc)
+        return Fit(self, h, D, noise=float(noise))
+
+    def laplace_fit(self, X, terms, jitter: float, lik, y, lik_param: float = 0.0, max_iter: int = 100,
+                    tol: float = 1e-12, a0=None, cap: int = 1024) -> "Fit":
+        """The latent posterior of the Laplace approximation, its mode found once and the factor of
+        B kept on the device (gaplac_laplace_fit_create): a Fit of kind "laplace" whose queries cost
+        the test rows' solve, not Newton steps or a factorisation. Arguments as laplace_logpdf; cap:
+        test points solved at once. A RuntimeWarning when the iteration did not converge (the Fit
+        then holds the last iterate)."""
+        keep, N, D, args = self._laplace_args(X, terms, jitter, lik, y, lik_param, max_iter, tol, a0)
+        h = c_void_p()
+        iters, conv, info = c_int32(), c_int32(), c_int64()
+        rc = self.lib.gaplac_laplace_fit_create(*args, int(cap), byref(h), byref(iters), byref(conv), byref(info))
+        self._check(rc)
+        self._laplace_warn(bool(conv.value), iters.value)
         return Fit(self, h, D)
 
     def posterior_components(self, X, terms, noise: float, y, Xs, comp, G=None):
@@ -721,18 +736,31 @@ class Fit:
     """A fitted posterior (gaplac_fit): the factor, z and alpha = C^{-1} y kept on the device by
     Context.fit. Queries cost the test rows' solve (mean_var) or a matrix-free product (mean), not
     a factorisation. Free it with close() or a with-block; a Fit outlives neither its Context's
-    close() (every query then raises ArgumentError) nor its own."""
+    close() (every query then raises ArgumentError) nor its own.
 
-    def __init__(self, ctx: Context, h: c_void_p, D: int):
+    kind "laplace" (Context.laplace_fit): the latent posterior of the Laplace approximation, the
+    factor that of B, alpha = grad log p(y | f) at the mode; .logq (= .logpdf), .iters, .converged,
+    .lik, .lik_param, .jitter and f_hat() besides."""
+
+    def __init__(self, ctx: Context, h: c_void_p, D: int, noise: float | None = None):
         self.ctx = ctx
         self.lib = ctx.lib
         self.h = h
         self.D = D
+        self.noise = noise
         n, cap = c_int64(), c_int64()
         lp, ld, q = c_double(), c_double(), c_double()
         self.lib.gaplac_fit_info(h, byref(n), byref(cap), byref(lp), byref(ld), byref(q))
         self.N, self.cap = n.value, cap.value
         self.logpdf, self.logdet, self.quad = lp.value, ld.value, q.value
+        lik, it, cv = c_int32(), c_int32(), c_int32()
+        lpar, jit = c_double(), c_double()
+        if self.lib.gaplac_fit_laplace_info(h, byref(lik), byref(lpar), byref(jit), byref(it), byref(cv)) == 0:
+            self.kind = "laplace"
+            self.lik, self.lik_param, self.jitter = lik.value, lpar.value, jit.value
+            self.logq, self.iters, self.converged = self.logpdf, it.value, bool(cv.value)
+        else:
+            self.kind = "exact"
 
     def close(self):
         if getattr(self, "h", None):
@@ -798,6 +826,79 @@ class Fit:
         self._check(self.lib.gaplac_fit_mean_var(h, M, Xsc.ctypes.data_as(c_void_p), max(M, 1),
                                                  mb.ctypes.data_as(c_void_p), vb.ctypes.data_as(c_void_p)))
         return mean, var
+
+    def f_hat(self) -> np.ndarray:
+        """The mode of a Laplace fit (gaplac_fit_mode); ArgumentError for an exact fit."""
+        h = self._handle()
+        out = np.empty(self.N, dtype=np.float64)
+        buf = out if self.N else np.empty(1)
+        self._check(self.lib.gaplac_fit_mode(h, buf.ctypes.data_as(c_void_p)))
+        return out
+
+    def mean_cov(self, Xs, noise_s: float = 0.0):
+        """(mean, cov) jointly at the rows of Xs, at most cap of them (gaplac_fit_mean_cov): cov =
+        K(xs) + noise_s I - V^T V, the full symmetric M x M matrix."""
+        h = self._handle()
+        Xsc = self._xs(Xs)
+        M = Xsc.shape[0]
+        mean = np.empty(M, dtype=np.float64)
+        cov = np.empty((M, M), dtype=np.float64, order="F")
+        mb = mean if M else np.empty(1)
+        cb = cov if M else np.empty(1)
+        self._check(self.lib.gaplac_fit_mean_cov(h, M, Xsc.ctypes.data_as(c_void_p), max(M, 1), float(noise_s),
+                                                 mb.ctypes.data_as(c_void_p), cb.ctypes.data_as(c_void_p), max(M, 1)))
+        return mean, cov
+
+    def predict(self, Xs, ys=None, Q: int = 32):
+        """Observation-space predictions at the rows of Xs: (ymean, yvar), and with ys the log
+        predictive density of each ys[j] as a third array. mean_var, then laplace_predict under the
+        fit's likelihood; an exact fit is the Gaussian case with lik_param = its noise."""
+        mean, var = self.mean_var(Xs)
+        if self.kind == "laplace":
+            return laplace_predict(self.lik, mean, var, ys, self.lik_param, Q)
+        if self.noise is None:
+            raise ArgumentError("the fit does not know its observation variance")
+        return laplace_predict(_native.LIK_GAUSSIAN, mean, var, ys, self.noise, Q)
+
+
+def gauss_hermite(Q: int):
+    """(nodes, weights) of the physicists' Gauss-Hermite rule of order Q (gaplac_gauss_hermite),
+    nodes ascending. Host arithmetic: no device is needed."""
+    lib = _native.load()
+    x = np.empty(max(int(Q), 1), dtype=np.float64)
+    w = np.empty(max(int(Q), 1), dtype=np.float64)
+    rc = lib.gaplac_gauss_hermite(int(Q), x.ctypes.data_as(c_void_p), w.ctypes.data_as(c_void_p))
+    if rc != 0:
+        raise ArgumentError(f"gaplac error {rc}: Q = {Q} is outside [1, 64]")
+    return x, w
+
+
+def laplace_predict(lik, mean, var, ys=None, lik_param: float = 0.0, Q: int = 32):
+    """Observation-space predictions from a latent (mean, var) under the likelihood lik
+    (gaplac_laplace_predict): (ymean, yvar), and with ys also logp, the log predictive density of
+    each ys[j], by Gauss-Hermite quadrature of order Q. Host arithmetic: no device is needed."""
+    lib = _native.load()
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    var = np.ascontiguousarray(var, dtype=np.float64)
+    if mean.ndim != 1 or var.shape != mean.shape:
+        raise ArgumentError(f"mean {mean.shape} and var {var.shape} must be vectors of one length")
+    M = mean.shape[0]
+    if ys is not None:
+        ys = np.ascontiguousarray(ys, dtype=np.float64)
+        if ys.shape != mean.shape:
+            raise ArgumentError(f"ys has shape {ys.shape}, expected {mean.shape}")
+    ym, yv, lp = (np.empty(max(M, 1), dtype=np.float64) for _ in range(3))
+    rc = lib.gaplac_laplace_predict(
+        likelihood_code(lik), float(lik_param), M, mean.ctypes.data_as(c_void_p), var.ctypes.data_as(c_void_p),
+        ys.ctypes.data_as(c_void_p) if ys is not None else None, int(Q), ym.ctypes.data_as(c_void_p),
+        yv.ctypes.data_as(c_void_p), lp.ctypes.data_as(c_void_p) if ys is not None else None)
+    if rc != 0:
+        what = {_native.E_PARAM: "a ys outside the likelihood's support (or a negative Gaussian variance)",
+                _native.E_KIND: "unknown likelihood", _native.E_ARG: "bad argument (Q outside [1, 64]?)"}
+        raise ArgumentError(f"gaplac error {rc}: {what.get(rc, '')}")
+    if ys is None:
+        return ym[:M], yv[:M]
+    return ym[:M], yv[:M], lp[:M]
 
 
 _default_ctx: Context | None = None

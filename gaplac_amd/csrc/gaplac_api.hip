@@ -20,6 +20,7 @@
 #include <cstring>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -2750,11 +2751,12 @@ struct FitDims {
     int64_t Np, ldl, nk, nkm, qc, Dm;
     int nt;
     int64_t L, dinv, X, Xs, part, mean, var, tp, alpha, elems;
+    int64_t sw, fhat;  // a Laplace fit (§10.15): sqrt(W) and the mode, before alpha (which stays last)
 };
 // test points per launch of the matrix-free mean (it needs no riding rows, so cap does not bind it)
 constexpr int64_t FIT_MEAN_CHUNK = 8192;
 
-static FitDims fit_dims(int64_t N, int32_t D, int64_t cap) {
+static FitDims fit_dims(int64_t N, int32_t D, int64_t cap, bool laplace = false) {
     FitDims d{};
     d.Np = round_up(N + 1, NB);
     d.nt = (int)(d.Np / NB);
@@ -2772,7 +2774,9 @@ static FitDims fit_dims(int64_t N, int32_t D, int64_t cap) {
     d.mean = d.part + std::max(2 * d.nk * cap, d.nkm * d.qc);
     d.var = d.mean + d.qc;
     d.tp = d.var + d.qc;
-    d.alpha = d.tp + (int64_t)((sizeof(TermPack) + 7) / 8);
+    d.sw = d.tp + (int64_t)((sizeof(TermPack) + 7) / 8);
+    d.fhat = d.sw + (laplace ? N : 0);
+    d.alpha = d.fhat + (laplace ? N : 0);
     d.elems = d.alpha + N;
     return d;
 }
@@ -2786,6 +2790,12 @@ struct gaplac_fit {
     double logpdf = NAN, logdet = NAN, quad = NAN;
     FitDims d{};
     double* buf = nullptr;
+    // kind 1: the latent posterior of the Laplace approximation (§10.15): the factor is B's, alpha
+    // is a = grad log p(y | f) at the mode, logpdf = log q, logdet = log|B|, quad = a^T f
+    int kind = 0;
+    int32_t lik = 0, iters = 0, converged = 0;
+    double lik_param = 0.0, jitter = 0.0;
+    std::vector<gaplac_term> terms;  // the caller's terms (the prior's Gram of an empty fit)
 };
 
 // The create-time launches after the evaluation: the factor's lower tiles out of the context's
@@ -2797,19 +2807,37 @@ static void fit_create_launches(hipStream_t s, const FitDims& d, int64_t N, cons
     launch_fit_backsub(s, buf + d.L, d.ldl, N, buf + d.alpha);
 }
 
-// One chunk of m <= cap test points (their inputs at d.Xs, ld m): K(xs, X) into the reserved
-// rows, the rows' solve against the factor, mean and variance into d.mean / d.var.
-static void fit_query_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, int W, double* buf) {
-    const int mt = (int)((m + NB - 1) / NB);
-    const TermPack* dtp = reinterpret_cast<const TermPack*>(buf + d.tp);
-    launch_cross_gram(s, buf + d.L, d.ldl, d.Np, d.nt, N, m, mt, buf + d.X, N, buf + d.Xs, m, dtp);
-    launch_fit_rows_solve(s, buf + d.L, d.ldl, d.nt, mt, W, buf + d.dinv);
-    launch_posterior(s, buf + d.L, d.ldl, d.Np, N, m, buf + d.Xs, m, dtp, buf + d.part, buf + d.mean, buf + d.var);
-}
-
 static void fit_mean_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, double* buf) {
     launch_fit_mean(s, N, m, buf + d.X, N, buf + d.alpha, buf + d.Xs, m,
                     reinterpret_cast<const TermPack*>(buf + d.tp), buf + d.part, buf + d.mean);
+}
+
+// One chunk of m <= cap test points (their inputs at d.Xs, ld m): K(xs, X) into the reserved
+// rows, the rows' solve against the factor, mean and variance into d.mean / d.var.
+// laplace: the rows are sw_n k(xs_j, x_n) below the factor of B; launch_posterior's variance is the
+// latent one, its V^T z mean is not the posterior's (row N of B's factor is no L^{-1} y) and is
+// overwritten by the matrix-free mean with a.
+static void fit_query_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, int W, double* buf,
+                               bool laplace = false) {
+    const int mt = (int)((m + NB - 1) / NB);
+    const TermPack* dtp = reinterpret_cast<const TermPack*>(buf + d.tp);
+    if (laplace)
+        launch_cross_gram_scaled(s, buf + d.L, d.ldl, d.Np, d.nt, N, m, mt, buf + d.X, N, buf + d.Xs, m, dtp,
+                                 buf + d.sw);
+    else
+        launch_cross_gram(s, buf + d.L, d.ldl, d.Np, d.nt, N, m, mt, buf + d.X, N, buf + d.Xs, m, dtp);
+    launch_fit_rows_solve(s, buf + d.L, d.ldl, d.nt, mt, W, buf + d.dinv);
+    launch_posterior(s, buf + d.L, d.ldl, d.Np, N, m, buf + d.Xs, m, dtp, buf + d.part, buf + d.mean, buf + d.var);
+    if (laplace) fit_mean_launches(s, d, N, m, buf);
+}
+
+// After a query's launches for m <= cap points (their rows solved below the factor, the mean in
+// d.mean): Sigma* = K(xs) + noise_s I - V^T V into the context's second workspace B (ld ldb), full
+// and symmetric. dtp: the pack with noise = noise_s.
+static void fit_cov_launches(hipStream_t s, const FitDims& d, int64_t N, int64_t m, double* buf, double* B,
+                             int64_t ldb, const TermPack* dtp) {
+    launch_post_cov(s, buf + d.L, d.ldl, d.Np, N, m, B, ldb, buf + d.Xs, m, buf + d.mean, dtp);
+    launch_mirror_lower(s, B, ldb, m);
 }
 
 static void fit_unregister(gaplac_fit* f) {
@@ -2835,6 +2863,7 @@ static int fit_create_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* 
     f->cap = cap;
     f->D = D;
     f->tp = tp;
+    f->terms.assign(terms, terms + T);
     if (N == 0) {  // the empty FiniteGP: its logpdf, and the prior at every query
         f->logpdf = -0.0;
         f->logdet = f->quad = 0.0;
@@ -2949,12 +2978,64 @@ static int fit_mean_var_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t
         const int64_t m = std::min(f->cap, M - r0);
         if ((rc = fit_upload_xs(f, r0, m, Xs, ldxs))) return rc;
         if ((rc = guarded_on(ctx, f->buf, (size_t)d.elems, nullptr, 0,
-                             [&] { fit_query_launches(s, d, f->N, m, ctx->spw, f->buf); })))
+                             [&] { fit_query_launches(s, d, f->N, m, ctx->spw, f->buf, f->kind == 1); })))
             return rc;
         if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean + r0, f->buf + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
         HIPCK(ctx, hipMemcpyAsync(out_var + r0, f->buf + d.var, (size_t)m * 8, hipMemcpyDeviceToHost, s));
         HIPCK(ctx, hipStreamSynchronize(s));
     }
+    return 0;
+}
+
+// The joint covariance of M <= cap test points from a fit of either kind (§10.15): the query's rows
+// and mean, then launch_post_cov + launch_mirror_lower reading the rows from the fit's buffer.
+static int fit_mean_cov_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                             double* out_mean, double* out_cov, int64_t ldc) {
+    if (!f || !f->ctx) return GAPLAC_E_ARG;
+    gaplac_ctx* ctx = f->ctx;
+    if (M < 0 || (out_cov && ldc < M))
+        return set_err(ctx, GAPLAC_E_ARG, "M = %lld < 0 or ldc %lld < M", (long long)M, (long long)ldc);
+    for (int64_t j = 0; j < M; ++j) {  // (rows M .. ldc-1 of out_cov are the caller's)
+        if (out_mean) out_mean[j] = NAN;
+        if (out_cov)
+            for (int64_t i = 0; i < M; ++i) out_cov[j * ldc + i] = NAN;
+    }
+    if (M > f->cap)
+        return set_err(ctx, GAPLAC_E_ARG, "M = %lld > cap = %lld: the joint covariance takes one chunk of test points",
+                       (long long)M, (long long)f->cap);
+    int rc = fit_query_check(f, M, Xs, ldxs);
+    if (rc < 0) return rc;
+    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
+        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
+    if (rc > 0) return 0;
+    if (!out_cov) return fit_mean_impl(f, M, Xs, ldxs, out_mean);
+    if (f->N == 0) {  // the prior
+        if ((rc = gaplac_gram(ctx, M, f->D, Xs, ldxs, (int32_t)f->terms.size(), f->terms.data(), noise_s, out_cov, ldc)))
+            return rc;
+        for (int64_t j = 0; j < M && out_mean; ++j) out_mean[j] = 0.0;
+        return 0;
+    }
+    HIPCK(ctx, hipSetDevice(f->device));
+    const FitDims& d = f->d;
+    hipStream_t s = ctx->s_main;
+    const int64_t ldb = round_up(M + 1, NB);
+    if ((rc = ensure(ctx, &ctx->B, &ctx->B_elems, (size_t)ldb * (size_t)ldb))) return rc;
+    if ((rc = fit_upload_xs(f, 0, M, Xs, ldxs))) return rc;
+    TermPack tp = f->tp;
+    tp.noise = noise_s;
+    *ctx->htp = tp;  // (nothing of the context's is in flight: every entry waits for its own work)
+    HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, s));
+    if ((rc = guarded_on(ctx, f->buf, (size_t)d.elems, ctx->B, ctx->B_elems, [&] {
+             fit_query_launches(s, d, f->N, M, ctx->spw, f->buf, f->kind == 1);
+             fit_cov_launches(s, d, f->N, M, f->buf, ctx->B, ldb, ctx->dtp);
+         }))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)ldb * 8, (size_t)M * 8, (size_t)M,
+                                hipMemcpyDeviceToHost, s));
+    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, f->buf + d.mean, (size_t)M * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(ctx, hipStreamSynchronize(s));
     return 0;
 }
 
@@ -3142,14 +3223,87 @@ struct LapGradOut {
     double* implicit;  // T + 1
 };
 
-// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs), gaplac_laplace_posterior_mean_var and
-// gaplac_laplace_logpdf_grad (grad: M = 0, the final factorisation carries identity rows).
+// gaplac_laplace_fit_create's request (§10.15): after the final factorisation a fit of kind 1 is
+// filled from the workspace and the vectors and handed out through *out.
+struct LapFitOut {
+    int64_t cap;
+    gaplac_fit** out;
+};
+
+// The handle of a Laplace fit before its buffer is filled (all of it for N = 0).
+static std::unique_ptr<gaplac_fit> lap_fit_new(gaplac_ctx* ctx, int64_t N, int32_t D, int32_t T,
+                                               const gaplac_term* terms, const TermPack& tp, int64_t cap, int32_t lik,
+                                               double lik_param, double jitter) {
+    std::unique_ptr<gaplac_fit> f(new gaplac_fit());
+    f->device = ctx->device;
+    f->N = N;
+    f->cap = cap;
+    f->D = D;
+    f->tp = tp;
+    f->tp.noise = jitter;
+    f->terms.assign(terms, terms + T);
+    f->kind = 1;
+    f->lik = lik;
+    f->lik_param = lik_param;
+    f->jitter = jitter;
+    return f;
+}
+
+// The create-time launches of a Laplace fit after the final factorisation: the factor's lower tiles
+// out of the workspace A (ld Np) and sw, f, a out of the vectors' buffer (alpha, the buffer's last
+// slot, written last: a buffer one element short is reported).
+static void lap_fit_create_launches(hipStream_t s, const FitDims& d, const LapDims& ld, int64_t N, const double* A,
+                                    const double* lap, double* buf) {
+    launch_fit_copy(s, A, d.Np, d.nt, buf + d.L, d.ldl);
+    launch_fit_vectors_copy(s, N, lap + ld.sw, lap + ld.f, lap + ld.a, buf + d.sw, buf + d.fhat, buf + d.alpha);
+}
+
+// The buffer of a Laplace fit out of the context after the final factorisation of B (ld Np in the
+// workspace, M = 0, no identity rows): the factor's lower tiles, Dinv, X and the pack as
+// fit_create_impl copies them, and sw, f, a out of the vectors' buffer.
+static int lap_fit_fill(gaplac_ctx* ctx, gaplac_fit* f, const LapDims& ld) {
+    const int64_t N = f->N;
+    f->d = fit_dims(N, f->D, f->cap, true);
+    const FitDims& d = f->d;
+    if (hipMalloc(reinterpret_cast<void**>(&f->buf), (size_t)d.elems * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        f->buf = nullptr;
+        return set_err(ctx, GAPLAC_E_OOM, "hipMalloc of the fit's %lld bytes failed", (long long)d.elems * 8);
+    }
+    hipStream_t s = ctx->s_main;
+    auto fail = [&](int rc) {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(f->buf);
+        f->buf = nullptr;
+        return rc;
+    };
+    int rc = guarded_on(ctx, f->buf, (size_t)d.elems, ctx->A, ctx->A_elems,
+                        [&] { lap_fit_create_launches(s, d, ld, N, ctx->A, ctx->lap, f->buf); }, ctx->lap, ctx->lap_elems);
+    if (rc) return fail(rc);
+    const struct {
+        int64_t dst;
+        const void* src;
+        size_t bytes;
+    } copies[] = {{d.dinv, ctx->Dinv, (size_t)d.nt * DINV_PER_BLOCK * 8},
+                  {d.X, ctx->dX, (size_t)N * f->D * 8},
+                  {d.tp, ctx->dtp, sizeof(TermPack)}};
+    for (const auto& c : copies)
+        if (c.bytes && hipMemcpyAsync(f->buf + c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return fail(set_err(ctx, GAPLAC_E_HIP, "copy into the fit's buffer: %s", hipGetErrorString(hipGetLastError())));
+    if (hipStreamSynchronize(s) != hipSuccess)
+        return fail(set_err(ctx, GAPLAC_E_HIP, "fit's buffer: %s", hipGetErrorString(hipGetLastError())));
+    return 0;
+}
+
+// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs), gaplac_laplace_posterior_mean_var,
+// gaplac_laplace_logpdf_grad (grad: M = 0, the final factorisation carries identity rows) and
+// gaplac_laplace_fit_create (fit: M = 0, the factor and the vectors are kept in a gaplac_fit).
 static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                         const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
                         int32_t max_iter, double tol, const double* a0, bool posterior, int64_t M, const double* Xs,
                         int64_t ldxs, double* out_logq, double* out_f, double* out_a, double* out_mean,
                         double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info,
-                        const LapGradOut* grad = nullptr) {
+                        const LapGradOut* grad = nullptr, const LapFitOut* fit = nullptr) {
     if (out_logq) *out_logq = NAN;
     if (grad) {
         if (grad->djitter) *grad->djitter = NAN;
@@ -3174,6 +3328,7 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     if (posterior && (M < 0 || (M > 0 && D > 0 && (!Xs || ldxs < M))))
         return set_err(ctx, GAPLAC_E_ARG, "M < 0, or Xs NULL / ldxs < M");
     if (!out_logq) return set_err(ctx, GAPLAC_E_ARG, "out_logq is NULL");
+    if (fit && fit->cap < 1) return set_err(ctx, GAPLAC_E_ARG, "cap = %lld < 1", (long long)fit->cap);
     if (lik != GAPLAC_LIK_GAUSSIAN && lik != GAPLAC_LIK_BERNOULLI && lik != GAPLAC_LIK_POISSON)
         return set_err(ctx, GAPLAC_E_KIND, "unknown likelihood %d", lik);
     if (!(jitter >= 0.0) || !std::isfinite(jitter))
@@ -3208,12 +3363,20 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
             if (out_mean) out_mean[j] = 0.0;
             if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
         }
+        if (fit) {  // the empty fit: the prior at every query
+            std::unique_ptr<gaplac_fit> f = lap_fit_new(ctx, 0, D, T, terms, tp, fit->cap, lik, lik_param, jitter);
+            f->logpdf = f->logdet = f->quad = 0.0;
+            f->converged = 1;
+            f->ctx = ctx;
+            ctx->fits.push_back(f.get());
+            *fit->out = f.release();
+        }
         return 0;
     }
     tp.noise = jitter;
     if (!posterior) M = 0;
     const LapDims d = lap_dims(N, M, grad != nullptr);
-    if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535)
+    if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535 || (fit && (fit->cap + NB - 1) / NB > 65535))
         return set_err(ctx, GAPLAC_E_OOM, "more than 65535 tile rows in one call");
     HIPCK(ctx, hipSetDevice(ctx->device));
     if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
@@ -3297,7 +3460,7 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(s, d, N, lik, lik_param, dy, lap); }))) return rc;
     if ((rc = lap_read_sums(ctx, d, h))) return rc;
     if (h[3] > 0.0) return lap_bad_w(ctx, N, h[3], out_info);
-    const double psi = h[2];
+    const double psi = h[2], atf = h[1];
     double logq = NAN;
     std::vector<double> quad;
     for (int64_t r0 = 0; r0 == 0 || r0 < M; r0 += LAP_CHUNK) {
@@ -3352,6 +3515,18 @@ static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     if (out_f) HIPCK(ctx, hipMemcpyAsync(out_f, lap + d.f, (size_t)N * 8, hipMemcpyDeviceToHost, s));
     if (out_a) HIPCK(ctx, hipMemcpyAsync(out_a, lap + d.a, (size_t)N * 8, hipMemcpyDeviceToHost, s));
     HIPCK(ctx, hipStreamSynchronize(s));
+    if (fit) {  // (M = 0, no gradient: the workspace holds B's factor with ld Np)
+        std::unique_ptr<gaplac_fit> f = lap_fit_new(ctx, N, D, T, terms, tp, fit->cap, lik, lik_param, jitter);
+        f->logpdf = logq;
+        f->logdet = r.logdet;
+        f->quad = atf;
+        f->iters = iters;
+        f->converged = converged ? 1 : 0;
+        if ((rc = lap_fit_fill(ctx, f.get(), d))) return rc;
+        f->ctx = ctx;
+        ctx->fits.push_back(f.get());
+        *fit->out = f.release();
+    }
     if (grad) {  // explicit (ctx->hgout, copied by the ending) + implicit
         for (int t = 0; t < T; ++t)
             if (grad->dparam) grad->dparam[t] = ctx->hgout[t] + himp[t];
@@ -3954,6 +4129,94 @@ int gaplac_fit_mean(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, 
 int gaplac_fit_mean_var(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
                         double* out_var) {
     return fit_mean_var_impl(fit, M, Xs, ldxs, out_mean, out_var);
+}
+
+int gaplac_fit_mean_cov(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double noise_s, double* out_mean,
+                        double* out_cov, int64_t ldc) {
+    return fit_mean_cov_impl(fit, M, Xs, ldxs, noise_s, out_mean, out_cov, ldc);
+}
+
+int gaplac_fit_mode(gaplac_fit* fit, double* out_f) {
+    if (!fit) return GAPLAC_E_ARG;
+    for (int64_t i = 0; out_f && i < fit->N; ++i) out_f[i] = NAN;
+    if (!fit->ctx) return GAPLAC_E_ARG;
+    if (fit->kind != 1) return set_err(fit->ctx, GAPLAC_E_ARG, "the fit is exact: it has no mode");
+    if (fit->N == 0) return 0;
+    if (!out_f) return set_err(fit->ctx, GAPLAC_E_ARG, "out_f is NULL");
+    HIPCK(fit->ctx, hipSetDevice(fit->device));
+    HIPCK(fit->ctx, hipMemcpy(out_f, fit->buf + fit->d.fhat, (size_t)fit->N * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int gaplac_fit_laplace_info(const gaplac_fit* fit, int32_t* out_lik, double* out_lik_param, double* out_jitter,
+                            int32_t* out_iters, int32_t* out_converged) {
+    if (!fit || fit->kind != 1) return GAPLAC_E_ARG;
+    if (out_lik) *out_lik = fit->lik;
+    if (out_lik_param) *out_lik_param = fit->lik_param;
+    if (out_jitter) *out_jitter = fit->jitter;
+    if (out_iters) *out_iters = fit->iters;
+    if (out_converged) *out_converged = fit->converged;
+    return 0;
+}
+
+int gaplac_laplace_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                              const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
+                              int32_t max_iter, double tol, const double* a0, int64_t cap, gaplac_fit** out,
+                              int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
+    if (out) *out = nullptr;
+    if (!ctx) return GAPLAC_E_ARG;
+    if (!out) return set_err(ctx, GAPLAC_E_ARG, "out is NULL");
+    const LapFitOut fo{cap, out};
+    double logq;
+    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0, nullptr, 0,
+                        &logq, nullptr, nullptr, nullptr, nullptr, out_iters, out_converged, out_info, nullptr, &fo);
+}
+
+// Host-only walk of a Laplace fit (no device needed; the iteration and its final factorisation are
+// gaplac_plan_check_laplace's): the create-time launches against the fit's buffer, one
+// mean-and-variance query of M points in chunks of cap (the scaled build, the rows' solve, the
+// norms and the matrix-free mean), one matrix-free mean query and one joint covariance of
+// min(M, cap) points against the context's second workspace, every launch through the functions
+// the entries call. short_ws 1: the fit's buffer one element short; 2: the covariance workspace.
+int gaplac_plan_check_laplace_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_t short_ws,
+                                  int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) {
+    if (N < 1 || cap < 1 || M < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
+    if ((cap + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
+    const FitDims d = fit_dims(N, 1, cap, true);
+    const LapDims ld = lap_dims(N, 0);
+    const int64_t mc = std::min(M, cap), ldb = round_up(mc + 1, NB);
+    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 44);
+    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 45);
+    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 46);
+    double* const fB = reinterpret_cast<double*>((uintptr_t)1 << 47);
+    LaunchGuard gc, gq;  // the create: buffer, workspace, vectors; the queries: buffer, second workspace
+    gc.base = gq.base = fb;
+    gc.elems = gq.elems = d.elems - (short_ws == 1 ? 1 : 0);
+    gc.base2 = fa;
+    gc.elems2 = ld.a_elems;
+    gc.base3 = fl;
+    gc.elems3 = ld.elems;
+    gq.base2 = fB;
+    gq.elems2 = ldb * ldb - (short_ws == 2 ? 1 : 0);
+    gc.dry = gq.dry = true;
+    {
+        GuardScope scope(&gc);
+        lap_fit_create_launches(nullptr, d, ld, N, fa, fl, fb);
+    }
+    {
+        GuardScope scope(&gq);
+        for (int64_t r0 = 0; r0 < M; r0 += cap)
+            fit_query_launches(nullptr, d, N, std::min(cap, M - r0), spw, fb, true);
+        for (int64_t r0 = 0; r0 < M; r0 += d.qc) fit_mean_launches(nullptr, d, N, std::min(d.qc, M - r0), fb);
+        if (mc > 0) {
+            fit_query_launches(nullptr, d, N, mc, spw, fb, true);
+            fit_cov_launches(nullptr, d, N, mc, fb, fB, ldb, nullptr);
+        }
+    }
+    if (out_launches) *out_launches = gc.launches + gq.launches;
+    if (out_violations) *out_violations = gc.violations + gq.violations;
+    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", (gc.violations ? gc.first : gq.first).c_str());
+    return 0;
 }
 
 // Host-only walk of a fit (no device needed): the create-time copy, z and the back-substitution
@@ -4593,6 +4856,185 @@ int gaplac_reset_stats(gaplac_ctx* ctx) {
     if (!ctx) return GAPLAC_E_ARG;
     ctx->stats = gaplac_stats{};
     ctx->evpairs.clear();
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// Observation-space predictions of the Laplace posterior: O(M) host
+// arithmetic, no context and no device.
+// ---------------------------------------------------------------------------------
+namespace {
+
+constexpr int GH_MAX_Q = 64;
+
+// Physicists' Gauss-Hermite rule of order Q (weight e^{-x^2}), ascending nodes: Newton on the
+// orthonormal Hermite recurrence in long double, from the largest root down (the usual asymptotic
+// first guesses), the negative half by symmetry.
+void gauss_hermite_ld(int Q, long double* x, long double* w) {
+    const long double pim4 = 0.7511255444649425L;  // pi^{-1/4}
+    const int half = (Q + 1) / 2;
+    long double z = 0.0L;
+    for (int i = 0; i < half; ++i) {
+        if (i == 0)
+            z = std::sqrt((long double)(2 * Q + 1)) - 1.85575L * std::pow((long double)(2 * Q + 1), -1.0L / 6.0L);
+        else if (i == 1)
+            z -= 1.14L * std::pow((long double)Q, 0.426L) / z;
+        else if (i == 2)
+            z = 1.86L * z - 0.86L * x[Q - 1];
+        else if (i == 3)
+            z = 1.91L * z - 0.91L * x[Q - 2];
+        else
+            z = 2.0L * z - x[Q + 1 - i];
+        long double pp = 1.0L;
+        for (int it = 0; it < 100; ++it) {
+            long double p1 = pim4, p2 = 0.0L;
+            for (int j = 0; j < Q; ++j) {
+                const long double p3 = p2;
+                p2 = p1;
+                p1 = z * std::sqrt(2.0L / (j + 1)) * p2 - std::sqrt((long double)j / (j + 1)) * p3;
+            }
+            pp = std::sqrt((long double)(2 * Q)) * p2;
+            const long double dz = p1 / pp;
+            z -= dz;
+            if (std::fabs(dz) <= 1e-19L * (1.0L + std::fabs(z))) break;
+        }
+        if (2 * i + 1 == Q) z = 0.0L;  // the middle node of an odd rule
+        {  // the derivative at the converged node
+            long double p1 = pim4, p2 = 0.0L;
+            for (int j = 0; j < Q; ++j) {
+                const long double p3 = p2;
+                p2 = p1;
+                p1 = z * std::sqrt(2.0L / (j + 1)) * p2 - std::sqrt((long double)j / (j + 1)) * p3;
+            }
+            pp = std::sqrt((long double)(2 * Q)) * p2;
+        }
+        x[Q - 1 - i] = z;
+        x[i] = -z;
+        w[i] = w[Q - 1 - i] = 2.0L / (pp * pp);
+    }
+}
+
+// Nodes and log weights of order Q in double, computed once per Q.
+struct GhRule {
+    bool ready = false;
+    double x[GH_MAX_Q], w[GH_MAX_Q], logw[GH_MAX_Q];
+};
+const GhRule& gh_rule(int Q) {
+    static GhRule rules[GH_MAX_Q + 1];
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    GhRule& r = rules[Q];
+    if (!r.ready) {
+        long double x[GH_MAX_Q], w[GH_MAX_Q];
+        gauss_hermite_ld(Q, x, w);
+        for (int q = 0; q < Q; ++q) {
+            r.x[q] = (double)x[q];
+            r.w[q] = (double)w[q];
+            r.logw[q] = (double)std::log(w[q]);
+        }
+        r.ready = true;
+    }
+    return r;
+}
+
+// log p(y | f) of the two non-Gaussian likelihoods, in the stable forms of the device's lik_eval.
+double host_lik_logp(int lik, double y, double f) {
+    if (lik == GAPLAC_LIK_BERNOULLI) return y * f - ((f > 0.0 ? f : 0.0) + std::log1p(std::exp(-std::fabs(f))));
+    return y * f - std::exp(f) - std::lgamma(y + 1.0);
+}
+double host_sigmoid(double f) {
+    const double e = std::exp(-std::fabs(f));
+    return f >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gaplac_gauss_hermite(int32_t Q, double* nodes, double* weights) {
+    if (Q < 1 || Q > GH_MAX_Q) return GAPLAC_E_ARG;
+    const GhRule& r = gh_rule(Q);
+    for (int q = 0; q < Q; ++q) {
+        if (nodes) nodes[q] = r.x[q];
+        if (weights) weights[q] = r.w[q];
+    }
+    return 0;
+}
+
+int gaplac_laplace_predict(int32_t lik, double lik_param, int64_t M, const double* mean, const double* var,
+                           const double* ys, int32_t Q, double* out_ymean, double* out_yvar, double* out_logp) {
+    if (M < 0) return GAPLAC_E_ARG;
+    for (int64_t j = 0; j < M; ++j) {
+        if (out_ymean) out_ymean[j] = NAN;
+        if (out_yvar) out_yvar[j] = NAN;
+        if (out_logp) out_logp[j] = NAN;
+    }
+    if (lik != GAPLAC_LIK_GAUSSIAN && lik != GAPLAC_LIK_BERNOULLI && lik != GAPLAC_LIK_POISSON) return GAPLAC_E_KIND;
+    if (M > 0 && (!mean || !var)) return GAPLAC_E_ARG;
+    if (lik == GAPLAC_LIK_GAUSSIAN) {
+        if (!(lik_param >= 0.0) || !std::isfinite(lik_param)) return GAPLAC_E_PARAM;
+    } else if (Q < 1 || Q > GH_MAX_Q) {
+        return GAPLAC_E_ARG;
+    }
+    for (int64_t j = 0; ys && j < M; ++j) {
+        const double v = ys[j];
+        const bool ok = lik == GAPLAC_LIK_BERNOULLI ? (v == 0.0 || v == 1.0)
+                        : lik == GAPLAC_LIK_POISSON ? (std::isfinite(v) && v >= 0.0 && v == std::floor(v))
+                                                    : std::isfinite(v);
+        if (!ok) return GAPLAC_E_PARAM;
+    }
+    const bool score = ys && out_logp;
+    const GhRule* rule = lik == GAPLAC_LIK_GAUSSIAN ? nullptr : &gh_rule(Q);
+    const double sqrt_pi = 1.7724538509055160273, half_log_pi = 0.57236494292470008707;
+    for (int64_t j = 0; j < M; ++j) {
+        const double mu = mean[j];
+        if (!std::isfinite(mu) || !std::isfinite(var[j])) continue;  // NaN at this point
+        const double v = var[j] > 0.0 ? var[j] : 0.0, sd = std::sqrt(v);
+        if (lik == GAPLAC_LIK_GAUSSIAN) {
+            const double s2 = v + lik_param, r = score ? ys[j] - mu : 0.0;
+            if (out_ymean) out_ymean[j] = mu;
+            if (out_yvar) out_yvar[j] = s2;
+            if (score) out_logp[j] = -0.5 * (1.8378770664093453 + std::log(s2)) - 0.5 * r * r / s2;
+            continue;
+        }
+        if (lik == GAPLAC_LIK_POISSON) {
+            const double ym = std::exp(mu + 0.5 * v);
+            if (out_ymean) out_ymean[j] = ym;
+            if (out_yvar) out_yvar[j] = ym + std::expm1(v) * ym * ym;
+        }
+        const bool need_p = lik == GAPLAC_LIK_BERNOULLI && (out_ymean || out_yvar);
+        if (sd == 0.0) {  // a point mass: the likelihood at mu itself
+            if (need_p) {
+                const double p = host_sigmoid(mu);
+                if (out_ymean) out_ymean[j] = p;
+                if (out_yvar) out_yvar[j] = p * (1.0 - p);
+            }
+            if (score) out_logp[j] = host_lik_logp(lik, ys[j], mu);
+            continue;
+        }
+        double t[GH_MAX_Q], tmax = -INFINITY, p = 0.0;
+        const double step = 1.4142135623730951 * sd;
+        for (int q = 0; q < Q; ++q) {
+            const double f = mu + step * rule->x[q];
+            if (need_p) p += rule->w[q] * host_sigmoid(f);
+            if (score) {
+                t[q] = rule->logw[q] + host_lik_logp(lik, ys[j], f);
+                tmax = t[q] > tmax ? t[q] : tmax;
+            }
+        }
+        if (need_p) {
+            p /= sqrt_pi;
+            if (out_ymean) out_ymean[j] = p;
+            if (out_yvar) out_yvar[j] = p * (1.0 - p);
+        }
+        if (score) {
+            double acc = 0.0;
+            for (int q = 0; q < Q; ++q) acc += std::exp(t[q] - tmax);
+            out_logp[j] = tmax + std::log(acc) - half_log_pi;
+        }
+    }
     return 0;
 }
 

@@ -369,6 +369,17 @@ void launch_laplace_anew(hipStream_t s, int64_t N, const double* b, const double
 // Y (N x M, ld ldy) = diag(sw) K(X, xs): the responses whose transpose rides below B.
 void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, int64_t ldx, const double* Xs,
                           int64_t ldxs, const TermPack* dtp, const double* sw, double* Y, int64_t ldy);
+// ---- fitted Laplace posterior ----
+// launch_cross_gram's rows (the same mt x nt tiles, grid and footprint) with column n times sw_n:
+// diag(sw) K(X, xs) transposed, below a kept factor of B. sw: N values in the same guarded
+// allocation as A (the fit's buffer).
+void launch_cross_gram_scaled(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t M, int mt,
+                              const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp,
+                              const double* sw);
+// sw, f, a (N values each, in the guard's third allocation: the iteration's vectors) into osw, of,
+// oa in its first (the fit's buffer).
+void launch_fit_vectors_copy(hipStream_t s, int64_t N, const double* sw, const double* f, const double* a, double* osw,
+                             double* of, double* oa);
 // ---- gradient of the Laplace log q ----
 // After a factorisation of B with identity rows (lda = 2 Np): row i of Y = L^{-T} times sw_i in
 // place (rows i < N, columns k < N), so that Y Y^T = R = sw B^{-1} sw, and dbinv_i = sum_{k >= i}

@@ -5741,6 +5741,67 @@ __global__ __launch_bounds__(256) void laplace_cross_kernel(int64_t N, int64_t M
     }
 }
 
+// The same scaled cross-covariances in the row layout of a fitted posterior:
+// tile (E, J) of the rows below a kept factor of B = sw_n k(xs_j, x_n), test rows E NB.., training
+// columns J NB..; 0 outside j < M, n < N. cross_gram_kernel's grid, tiling and arithmetic per
+// entry (two test points per lane, one 16-byte store per column, the tile's 128 training
+// coordinates staged in LDS) with the tile's 128 values of sw staged beside them and each stored
+// value multiplied once by its column's, in laplace_cross_kernel's order sw_n * tot.
+__global__ __launch_bounds__(256) void cross_gram_scaled_kernel(double* __restrict__ A, int64_t lda, int64_t Np,
+                                                                int64_t N, int64_t M, const double* __restrict__ X,
+                                                                int64_t ldx, const double* __restrict__ Xs,
+                                                                int64_t ldxs, const TermPack* __restrict__ tpp,
+                                                                const double* __restrict__ sw) {
+    __shared__ double xcol[GAPLAC_MAX_TERMS][NB];
+    __shared__ double swc[NB];
+    const TermPack& tp = *tpp;
+    const int T = tp.T;
+    const int J = (int)blockIdx.x, E = (int)blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t c0 = (int64_t)J * NB;
+    for (int idx = tid; idx < T * NB; idx += 256) {
+        const int t = idx / NB, c = idx % NB;
+        xcol[t][c] = (c0 + c < N && tp.kind[t] != GAPLAC_NOISE) ? X[(int64_t)tp.col[t] * ldx + c0 + c] : 0.0;
+    }
+    if (tid < NB) swc[tid] = c0 + tid < N ? sw[c0 + tid] : 0.0;
+    const int64_t j0 = (int64_t)E * NB + 2 * lane;  // test points j0, j0 + 1
+    double xa[GAPLAC_MAX_TERMS], xb[GAPLAC_MAX_TERMS];
+#pragma unroll
+    for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+        xa[t] = 0.0;
+        xb[t] = 0.0;
+        if (t < T && tp.kind[t] != GAPLAC_NOISE) {
+            const double* xc = Xs + (int64_t)tp.col[t] * ldxs;
+            if (j0 < M) xa[t] = xc[j0];
+            if (j0 + 1 < M) xb[t] = xc[j0 + 1];
+        }
+    }
+    __syncthreads();
+    double* base = A + c0 * lda + Np + j0;
+    for (int cc = w; cc < NB; cc += 4) {
+        double tot0 = 0.0, tot1 = 0.0, pr0 = 1.0, pr1 = 1.0;
+#pragma unroll
+        for (int t = 0; t < GAPLAC_MAX_TERMS; ++t) {
+            if (t < T) {
+                const int kind = tp.kind[t];
+                const double p = tp.p[t], xj = xcol[t][cc];
+                pr0 *= kind == GAPLAC_NOISE ? 0.0 : term_k(kind, p, xa[t], xj, false);
+                pr1 *= kind == GAPLAC_NOISE ? 0.0 : term_k(kind, p, xb[t], xj, false);
+                if (tp.last_in_group[t]) {
+                    tot0 += pr0;
+                    tot1 += pr1;
+                    pr0 = 1.0;
+                    pr1 = 1.0;
+                }
+            }
+        }
+        const bool colok = c0 + cc < N;
+        const double sn = swc[cc];
+        const double o0 = (colok && j0 < M) ? sn * tot0 : 0.0, o1 = (colok && j0 + 1 < M) ? sn * tot1 : 0.0;
+        *reinterpret_cast<double2*>(base + (int64_t)cc * lda) = make_double2(o0, o1);
+    }
+}
+
 // Launchers. The vectors live in one buffer of the context (the guard's second allocation), the
 // matrix in its workspace (the first), the response matrix of the test points in a third.
 void launch_laplace_lik(hipStream_t s, int64_t N, int lik, double param, const double* y, const double* a,
@@ -5808,6 +5869,40 @@ void launch_laplace_cross(hipStream_t s, int64_t N, int64_t M, const double* X, 
     if (!ok) return;
     laplace_cross_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)((M + LAP_CROSS_MJ - 1) / LAP_CROSS_MJ)),
                            dim3(256), 0, s>>>(N, M, X, ldx, Xs, ldxs, dtp, sw, Y, ldy);
+}
+
+// sw, f and a (N values each) out of the iteration's vectors into a Laplace fit's buffer.
+__global__ __launch_bounds__(256) void fit_vectors_copy_kernel(int64_t N, const double* __restrict__ sw,
+                                                               const double* __restrict__ f,
+                                                               const double* __restrict__ a, double* __restrict__ osw,
+                                                               double* __restrict__ of, double* __restrict__ oa) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    osw[i] = sw[i];
+    of[i] = f[i];
+    oa[i] = a[i];
+}
+
+void launch_fit_vectors_copy(hipStream_t s, int64_t N, const double* sw, const double* f, const double* a, double* osw,
+                             double* of, double* oa) {
+    if (N <= 0) return;
+    bool ok = true;
+    for (const double* p : {(const double*)osw, (const double*)of, (const double*)oa})
+        ok = guard_launch("fit_vectors_copy_kernel", p, 0, N) && ok;
+    for (const double* p : {sw, f, a}) ok = guard_launch("fit_vectors_copy_kernel (source)", p, 0, N, 2) && ok;
+    if (!ok) return;
+    fit_vectors_copy_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s>>>(N, sw, f, a, osw, of, oa);
+}
+
+void launch_cross_gram_scaled(hipStream_t s, double* A, int64_t lda, int64_t Np, int nt, int64_t N, int64_t M, int mt,
+                              const double* X, int64_t ldx, const double* Xs, int64_t ldxs, const TermPack* dtp,
+                              const double* sw) {
+    if (nt <= 0 || mt <= 0) return;
+    bool ok = guard_launch("cross_gram_scaled_kernel", A, 0, ((int64_t)nt * NB - 1) * lda + Np + (int64_t)mt * NB);
+    ok = guard_launch("cross_gram_scaled_kernel (sw)", sw, 0, N) && ok;
+    if (!ok) return;
+    cross_gram_scaled_kernel<<<dim3((unsigned)nt, (unsigned)mt), dim3(256), 0, s>>>(A, lda, Np, N, M, X, ldx, Xs, ldxs,
+                                                                                    dtp, sw);
 }
 
 // ---------------------------------------------------------------------------------

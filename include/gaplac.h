@@ -307,6 +307,61 @@ int gaplac_laplace_logpdf_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const doub
                                double* out_djitter,
                                double* out_implicit /* T + 1: the implicit parts of dparam and djitter, may be NULL */);
 
+/* Fitted Laplace posterior: gaplac_laplace_logpdf's iteration (same arguments, checks, return
+ * codes; f, a, log q, iters and converged bitwise that entry's), after whose final factorisation
+ * the factor of B = I + sqrt(W) K~ sqrt(W), the diagonal blocks' inverses, X, the terms (noise =
+ * jitter), sqrt(W), the mode f and a = grad log p(y | f) move into a gaplac_fit with room for cap
+ * test rows, as gaplac_fit_create does for the exact posterior. The handle is the same type with a
+ * kind inside: gaplac_fit_destroy, the context's bookkeeping and every query take both kinds.
+ *   gaplac_fit_info      logpdf := log q, logdet := log|B|, quad := a^T f
+ *   gaplac_fit_alpha     a (no back-substitution: a is the iteration's)
+ *   gaplac_fit_mean      sum_n k(xs_j, x_n) a_n, matrix-free
+ *   gaplac_fit_mean_var  per chunk of cap points the rows sqrt(W_n) k(xs_j, x_n) are written below
+ *                        the kept factor and solved against it; var_j = k(xs_j, xs_j) - |V_j|^2, the
+ *                        mean the matrix-free one
+ * Not converged is not an error (the handle holds the last iterate, *out_converged = 0). A failed
+ * factorisation of B gives info > 0 and no handle (*out = NULL). GAPLAC_E_ARG also for cap < 1 or
+ * out NULL. N = 0: a fit that returns the prior. The context's workspace is free afterwards. */
+int gaplac_laplace_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx,
+                              int32_t T, const gaplac_term* terms, double jitter, int32_t lik,
+                              double lik_param, const double* y, int32_t max_iter, double tol,
+                              const double* a0 /* NULL: 0 */, int64_t cap, gaplac_fit** out,
+                              int32_t* out_iters, int32_t* out_converged, int64_t* out_info);
+/* The mode f (N values) of a Laplace fit. GAPLAC_E_ARG for a NULL or an exact fit. */
+int gaplac_fit_mode(gaplac_fit* fit, double* out_f);
+/* What a Laplace fit was created with and how its iteration ended; any pointer may be NULL.
+ * GAPLAC_E_ARG for a NULL or an exact fit. */
+int gaplac_fit_laplace_info(const gaplac_fit* fit, int32_t* out_lik, double* out_lik_param,
+                            double* out_jitter, int32_t* out_iters, int32_t* out_converged);
+/* Mean and joint covariance at M <= cap test points from a fit of either kind: the query's rows,
+ * then Sigma* = K(xs) + noise_s I - V^T V, full and exactly symmetric (M x M column-major, leading
+ * dimension ldc), in the format of gaplac_posterior_mean_cov, formed in the context's second
+ * workspace. out_mean may be NULL; out_cov NULL gives the matrix-free mean. Outputs are NaN-filled
+ * first. GAPLAC_E_ARG for M > cap (the message says so), noise_s < 0 or non-finite, ldc < M, a
+ * NULL fit or one whose context is gone, and as the other queries. N = 0: the prior's Gram. */
+int gaplac_fit_mean_cov(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                        double* out_mean, double* out_cov, int64_t ldc);
+
+/* Observation-space predictions from a latent (mean, var): host arithmetic, no context, no device.
+ * gaplac_gauss_hermite: the physicists' Gauss-Hermite rule of order 1 <= Q <= 64 (weight e^{-x^2},
+ * ascending nodes; either output may be NULL), computed once per Q in long double by Newton on the
+ * orthonormal Hermite recurrence. GAPLAC_E_ARG for Q outside [1, 64].
+ * gaplac_laplace_predict: per point, v = max(var, 0), sigma = sqrt(v) and
+ *   int h(f) N(f | mean, v) df ~ pi^{-1/2} sum_q w_q h(mean + sqrt(2) sigma x_q):
+ *   GAUSSIAN   ymean = mean, yvar = v + lik_param, logp = log N(ys; mean, v + lik_param) (Q unused)
+ *   POISSON    ymean = exp(mean + v/2), yvar = ymean + expm1(v) ymean^2 (closed forms),
+ *              logp = logsumexp_q[log w_q + ys f_q - e^{f_q} - lgamma(ys + 1)] - log(pi)/2
+ *   BERNOULLI  ymean = p = pi^{-1/2} sum_q w_q sigma(f_q), yvar = p (1 - p),
+ *              logp = logsumexp_q[log w_q + ys f_q - log(1 + e^{f_q})] - log(pi)/2
+ * v = 0 gives log p(ys | mean) itself. ys NULL: no score. Every output may be NULL; outputs are
+ * NaN-filled first and stay NaN at a point whose mean or variance is not finite. GAPLAC_E_KIND for
+ * an unknown lik; GAPLAC_E_PARAM for a ys outside the likelihood's support or a Gaussian variance
+ * < 0; GAPLAC_E_ARG for M < 0, mean or var NULL with M > 0, or Q outside [1, 64] (non-Gaussian). */
+int gaplac_gauss_hermite(int32_t Q, double* nodes, double* weights);
+int gaplac_laplace_predict(int32_t lik, double lik_param, int64_t M, const double* mean,
+                           const double* var, const double* ys /* NULL: no score */, int32_t Q,
+                           double* out_ymean, double* out_yvar, double* out_logp);
+
 /* One draw of the FiniteGP: out = L z with C = K(X) + noise I = L L^T
  * and z the N standard-normal values the caller drew (the host keeps the RNG stream, so a
  * given z gives the same sample as the reference). Replaces: rand(rng, FiniteGP(GP(k), X,
@@ -661,6 +716,15 @@ int gaplac_plan_check_laplace(int64_t N, int64_t M, int32_t spw, int32_t short_w
  * reference. */
 int gaplac_plan_check_laplace_grad(int64_t N, int32_t spw, int32_t short_ws, int64_t* out_launches,
                                    int64_t* out_violations, char* msg, int64_t msglen);
+/* The same check for a Laplace fit (the iteration and its final factorisation are
+ * gaplac_plan_check_laplace's): the create-time launches after the final factorisation, one
+ * mean-and-variance query of M points in chunks of cap with the scaled build of the rows, one
+ * matrix-free mean and one gaplac_fit_mean_cov of min(M, cap) points. short_ws 1: the fit's buffer
+ * one element short; 2: the covariance workspace. GAPLAC_E_ARG for N < 1, cap < 1, M < 0, spw
+ * outside [1, 8], short_ws outside [0, 2]. */
+int gaplac_plan_check_laplace_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_t short_ws,
+                                  int64_t* out_launches, int64_t* out_violations, char* msg,
+                                  int64_t msglen);
 /* The same check for gaplac_sparse_elbo_grad: gaplac_plan_check_sparse at Ms = 0, then the
  * gradient's launches: the order-Mz ones against its scratch, alpha and the product kernel against
  * the first workspace and the scratch. short_ws 1: the first workspace one element short; 2: the

@@ -22,11 +22,17 @@
 //                                the preloaded factorisation of order Ms, plain or with riding rows;
 //   gaplac_plan_check_fit      - the fitted posterior: the tile copy and back-substitution of its
 //                                creation and its two queries against the fit's own buffer;
+//   gaplac_plan_check_laplace_fit - the fitted Laplace posterior: the create-time launches, the
+//                                queries with the scaled build and the joint covariance against the
+//                                fit's buffer and the second workspace;
+//   gaplac_gauss_hermite / gaplac_laplace_predict - the observation-space predictions' host
+//                                arithmetic over their edge cases;
 //   gaplac_plan_check_schedule - the deferred-update accounting at every depth;
 //   gaplac_dist_plan_check     - build_plan / check_plan of the distributed schedule;
 //   gaplac_dist_plan           - the plan export;
 //   gaplac_dist_plan_check_tail / gaplac_dist_plan_tail - the same with the tail gather.
 // Exit 0 when every check passes and no sanitizer fired (halt_on_error=1).
+#include <cmath>
 #include <cstdio>
 #include <vector>
 
@@ -223,6 +229,65 @@ int main() {
             }
     EXPECT(gaplac_plan_check_laplace_grad(0, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG,
            "laplace gradient: N = 0 accepted");
+    // the fitted Laplace posterior: create, a query of M points in chunks of cap, a matrix-free mean
+    // and a joint covariance of min(M, cap) points; then the fit's buffer (1) and the covariance
+    // workspace (2) one element short
+    for (int spw : {1, 4, 8})
+        for (int64_t N : {1, 5, 127, 128, 129, 300, 1000, 4096, 10239, 10240, 16384})
+            for (int64_t cap : {1, 128, 129, 1024})
+                for (int64_t M : {(int64_t)1, cap, cap + 1, 5 * cap + 3})
+                    for (int short_ws : {0, 1, 2}) {
+                        const int rc = gaplac_plan_check_laplace_fit(N, cap, M, spw, short_ws, &a, &b, msg, sizeof msg);
+                        EXPECT(rc == 0 && a > 0 && (short_ws ? b >= 1 : b == 0),
+                               "plan_check_laplace_fit N=%lld cap=%lld M=%lld spw=%d short_ws=%d: rc %d violations %lld %s",
+                               (long long)N, (long long)cap, (long long)M, spw, short_ws, rc, (long long)b, msg);
+                        ++checks;
+                    }
+    EXPECT(gaplac_plan_check_laplace_fit(10, 0, 1, 4, 0, &a, &b, msg, sizeof msg) == GAPLAC_E_ARG,
+           "laplace fit: cap = 0 accepted");
+    EXPECT(gaplac_fit_mode(nullptr, nullptr) == GAPLAC_E_ARG && gaplac_fit_mean_cov(nullptr, 0, nullptr, 0, 0.0, nullptr, nullptr, 0) == GAPLAC_E_ARG,
+           "laplace fit: a NULL handle accepted");
+    // the observation-space predictions: every order's rule, then the edge cases of every likelihood
+    for (int Q = 1; Q <= 64; ++Q) {
+        double x[64], w[64], sum = 0.0;
+        EXPECT(gaplac_gauss_hermite(Q, x, w) == 0, "gauss_hermite Q=%d", Q);
+        for (int q = 0; q < Q; ++q) sum += w[q];
+        for (int q = 1; q < Q; ++q) EXPECT(x[q] > x[q - 1], "gauss_hermite Q=%d: nodes not ascending at %d", Q, q);
+        EXPECT(std::fabs(sum - 1.7724538509055160) <= 1e-14, "gauss_hermite Q=%d: weights sum to %.17g", Q, sum);
+        ++checks;
+    }
+    EXPECT(gaplac_gauss_hermite(0, nullptr, nullptr) == GAPLAC_E_ARG && gaplac_gauss_hermite(65, nullptr, nullptr) == GAPLAC_E_ARG,
+           "gauss_hermite: a bad order accepted");
+    {
+        const double mean[] = {0.3, -40.0, 40.0, 9.0, NAN, 0.1, -2.0, 700.0};
+        const double var[] = {0.2, 1.0, 1.0, 0.0, 0.5, INFINITY, -1e-14, 3.0};
+        const double ysb[] = {1, 0, 1, 0, 1, 0, 1, 0}, ysp[] = {0, 3, 1e4, 7, 1, 2, 0, 5}, ysg[] = {0.1, -3, 2, 9, 0, 1, 2, 3};
+        const double bad[] = {1, 0, 0.5, 0, 1, 0, 1, 0};
+        double ym[8], yv[8], lp[8];
+        for (int lik : {GAPLAC_LIK_GAUSSIAN, GAPLAC_LIK_BERNOULLI, GAPLAC_LIK_POISSON})
+            for (int Q : {1, 2, 20, 32, 64})
+                for (int64_t M : {0, 1, 8})
+                    for (int outs = 0; outs < 8; ++outs)
+                        for (int score : {0, 1}) {
+                            const double* ys = !score ? nullptr : lik == GAPLAC_LIK_BERNOULLI ? ysb : lik == GAPLAC_LIK_POISSON ? ysp : ysg;
+                            const int rc = gaplac_laplace_predict(lik, 0.1, M, mean, var, ys, Q, outs & 1 ? ym : nullptr,
+                                                                  outs & 2 ? yv : nullptr, outs & 4 ? lp : nullptr);
+                            EXPECT(rc == 0, "laplace_predict lik=%d Q=%d M=%lld outs=%d: rc %d", lik, Q, (long long)M, outs, rc);
+                            if (rc == 0 && M == 8 && outs == 7 && score) {
+                                EXPECT(std::isnan(ym[4]) && std::isnan(yv[5]) && std::isnan(lp[4]) && std::isnan(lp[5]),
+                                       "laplace_predict lik=%d: a non-finite input did not give NaN", lik);
+                                EXPECT(std::isfinite(lp[0]) && std::isfinite(lp[1]) && std::isfinite(lp[2]) && std::isfinite(lp[3]) &&
+                                           std::isfinite(lp[6]),
+                                       "laplace_predict lik=%d Q=%d: a finite input gave a non-finite score", lik, Q);
+                            }
+                            ++checks;
+                        }
+        EXPECT(gaplac_laplace_predict(GAPLAC_LIK_BERNOULLI, 0.0, 8, mean, var, bad, 32, ym, yv, lp) == GAPLAC_E_PARAM,
+               "laplace_predict: ys outside the support accepted");
+        EXPECT(gaplac_laplace_predict(9, 0.0, 8, mean, var, nullptr, 32, ym, yv, lp) == GAPLAC_E_KIND, "laplace_predict: lik 9 accepted");
+        EXPECT(gaplac_laplace_predict(GAPLAC_LIK_POISSON, 0.0, 8, mean, var, nullptr, 65, ym, yv, lp) == GAPLAC_E_ARG,
+               "laplace_predict: Q = 65 accepted");
+    }
     for (int depth = 0; depth <= 8; ++depth) {
         if (depth == 1) continue;
         for (int ext : {0, 1})
