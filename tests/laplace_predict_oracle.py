@@ -7,7 +7,7 @@ With v = max(var, 0), s = sqrt(v), (x_q, w_q) = numpy.polynomial.hermite.hermgau
     gaussian   ymean = mean, yvar = v + param, logp = log N(ys; mean, v + param)
     poisson    ymean = exp(mean + v/2), yvar = ymean + expm1(v) ymean^2,
                logp = logsumexp_q[log w_q + ys f_q - e^{f_q} - lgamma(ys + 1)] - log(pi) / 2
-    bernoulli  ymean = p = pi^{-1/2} sum_q w_q sigma(f_q), yvar = p (1 - p),
+    bernoulli  ymean = p = min(1, pi^{-1/2} sum_q w_q sigma(f_q)), yvar = p (1 - p),
                logp = logsumexp_q[log w_q + ys f_q - log(1 + e^{f_q})] - log(pi) / 2
 """
 import numpy as np
@@ -45,7 +45,9 @@ def predict(lik, mean, var, ys=None, lik_param=0.0, Q=32):
             ymean = np.exp(mu + 0.5 * v)
             yvar = ymean + np.expm1(v) * ymean * ymean
         else:
-            ymean = (scipy.special.expit(f) @ w) / np.sqrt(np.pi)
+            # (the rounded weights sum to sqrt(pi) (1 + 2^-52): where every sigma(f_q) is 1 the sum
+            # is one ulp above 1 and p (1 - p) negative; a probability is at most 1)
+            ymean = np.minimum((scipy.special.expit(f) @ w) / np.sqrt(np.pi), 1.0)
             yvar = ymean * (1.0 - ymean)
         if ys is not None:
             t = np.log(w)[None, :] + lik_logp(lik, np.asarray(ys, dtype=np.float64)[:, None], f)
