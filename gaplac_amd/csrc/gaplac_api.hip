@@ -1462,17 +1462,7 @@ int guarded(gaplac_ctx* ctx, bool with_B, Launches&& launches) {
 template <typename Launches>
 int guarded_on(gaplac_ctx* ctx, const double* base, size_t elems, const double* base2, size_t elems2,
                Launches&& launches, const double* base3, size_t elems3) {
-    LaunchGuard g;
-    g.base = base;
-    g.elems = (int64_t)elems;
-    if (base2) {
-        g.base2 = base2;
-        g.elems2 = (int64_t)elems2;
-    }
-    if (base3) {
-        g.base3 = base3;
-        g.elems3 = (int64_t)elems3;
-    }
+    LaunchGuard g{base, (int64_t)elems, base2, (int64_t)elems2, base3, (int64_t)elems3};
     {
         GuardScope scope(&g);
         launches();
@@ -1753,16 +1743,6 @@ int logpdf_multi_impl(gaplac_ctx* ctx, bool on_device, int64_t N, int32_t D, con
 }
 
 // ---- joint posterior at test points ----
-// Argument checks the three entries share, after their own (sizes and output pointers).
-int joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise, const double* y,
-                int64_t M, const double* Xs, int64_t ldxs, double noise_s) {
-    int rc = check_common(ctx, N, D, X, ldx, noise, y);
-    if (rc) return rc;
-    if (M > 0 && D > 0 && (!Xs || ldxs < M)) return set_err(ctx, GAPLAC_E_ARG, "Xs NULL or ldxs < M");
-    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
-        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
-    return 0;
-}
 
 // The second factorisation runs in B: A and B change places for as long as this lives.
 // (Given another workspace, A changes places with that one: the sparse joint entries' third, §10.11.)
@@ -1854,113 +1834,6 @@ int joint_factor(gaplac_ctx* ctx, int64_t M, int32_t D, const TermPack& tp, cons
     if (rc) return rc;
     if ((rc = finish(*r, nullptr, nullptr, nullptr)))
         return set_err(ctx, rc, "%s is not positive definite (leading minor %d)", what, rc);
-    return 0;
-}
-
-int posterior_mean_cov_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                            const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
-                            int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
-    if (!ctx) return GAPLAC_E_ARG;
-    if (M < 0 || (out_cov && ldc < M)) return set_err(ctx, GAPLAC_E_ARG, "M = %lld < 0 or ldc < M", (long long)M);
-    for (int64_t j = 0; j < M; ++j) {  // (rows M .. ldc-1 of out_cov are the caller's)
-        if (out_mean) out_mean[j] = NAN;
-        if (out_cov)
-            for (int64_t i = 0; i < M; ++i) out_cov[j * ldc + i] = NAN;
-    }
-    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (M == 0) return 0;
-    if (N == 0) {  // the posterior of an empty FiniteGP is the prior
-        if (out_cov && (rc = gaplac_gram(ctx, M, D, Xs, ldxs, T, terms, noise_s, out_cov, ldc))) return rc;
-        for (int64_t j = 0; j < M && out_mean; ++j) out_mean[j] = 0.0;
-        return 0;
-    }
-    tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, out_cov ? Cov::full : Cov::none)))
-        return rc;
-    if (out_cov)
-        HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)joint_dims(N, M, 0).ldb * 8,
-                                    (size_t)M * 8, (size_t)M, hipMemcpyDeviceToHost, ctx->s_main));
-    if (out_mean)
-        HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->s_main));
-    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
-    return 0;
-}
-
-int posterior_rand_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                        const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
-                        int64_t ldxs, double noise_s, int64_t R, const double* Z, int64_t ldz, double* out,
-                        int64_t ldo) {
-    if (!ctx) return GAPLAC_E_ARG;
-    if (M < 0 || R < 0 || !out || ldz < M || ldo < M || (R > 0 && M > 0 && !Z))
-        return set_err(ctx, GAPLAC_E_ARG, "M < 0, R < 0, Z / out NULL, or ldz / ldo < M");
-    for (int64_t r = 0; r < R; ++r)  // (rows M .. ldo-1 of out are the caller's)
-        for (int64_t i = 0; i < M; ++i) out[r * ldo + i] = NAN;
-    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (M == 0 || R == 0) return 0;
-    if (N == 0)  // the prior at the test points
-        return gaplac_rand_multi(ctx, M, D, Xs, ldxs, T, terms, noise_s, R, Z, ldz, out, ldo);
-    tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, 0, Cov::lower))) return rc;
-    const int64_t Mp = joint_dims(N, M, 0).Mp;
-    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Mp * (size_t)R))) return rc;
-    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)M * (size_t)R))) return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Mp * 8, Z, (size_t)ldz * 8, (size_t)M * 8, (size_t)R,
-                                hipMemcpyHostToDevice, ctx->s_main));
-    WsSwap swap(ctx);  // from here on ctx->A is the order-M workspace
-    EvalResult r2;
-    if ((rc = joint_factor(ctx, M, D, tp, ExtraRows{}.on_prebuilt(), &r2))) return rc;
-    if ((rc = guarded(ctx, false,
-                      [&] { draws_launches(ctx->s_main, ctx->A, Mp, M, ctx->dZ, R, ctx->dO, ctx->pmean); })))
-        return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)M * 8, (size_t)M * 8, (size_t)R,
-                                hipMemcpyDeviceToHost, ctx->s_main));
-    HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
-    return 0;
-}
-
-int posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                          const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
-                          int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys, double* out_logpdf,
-                          double* out_logdet, double* out_quad) {
-    if (!ctx) return GAPLAC_E_ARG;
-    if (M < 0 || R < 0 || !out_logpdf || ldys < M || (R > 0 && M > 0 && !Ys))
-        return set_err(ctx, GAPLAC_E_ARG, "M < 0, R < 0, Ys / out_logpdf NULL, or ldys < M");
-    if (M > 0 && R > 0) {  // (an empty call writes nothing)
-        for (int64_t r = 0; r < R; ++r) {
-            out_logpdf[r] = NAN;
-            if (out_quad) out_quad[r] = NAN;
-        }
-        if (out_logdet) *out_logdet = NAN;
-    }
-    int rc = joint_check(ctx, N, D, X, ldx, noise, y, M, Xs, ldxs, noise_s);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (M == 0 || R == 0) return 0;
-    if (N == 0)  // the prior at the test points
-        return gaplac_logpdf_multi(ctx, M, D, Xs, ldxs, T, terms, noise_s, R, Ys, ldys, out_logpdf, out_logdet,
-                                   out_quad);
-    if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
-        return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
-    tp.noise = noise;
-    if ((rc = joint_stages(ctx, N, D, X, ldx, tp, y, M, Xs, ldxs, noise_s, R, Cov::lower))) return rc;
-    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)M * (size_t)R))) return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)M * 8, Ys, (size_t)ldys * 8, (size_t)M * 8, (size_t)R,
-                                hipMemcpyHostToDevice, ctx->s_main));
-    WsSwap swap(ctx);
-    // the rows hold (Ys - m 1^T)^T and ride along as the responses of gaplac_logpdf_multi do
-    EvalResult r2;
-    if ((rc = joint_factor(ctx, M, D, tp, ExtraRows::responses(R, ctx->dY, M, ctx->pmean).on_prebuilt(), &r2)))
-        return rc;
-    if (out_logdet) *out_logdet = r2.logdet;
-    if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
-    HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2396,17 +2269,6 @@ void sparse_joint_cov_launches(hipStream_t s, const SparseDims& d, const SparseJ
     if (mirror) launch_mirror_lower(s, C, j.ldc, Ms);
 }
 
-// Argument checks the three entries share, after their own (sizes and output pointers).
-int sparse_joint_check(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, double noise,
-                       const double* y, int64_t Mz, const double* Z, int64_t ldz, double jitter, int64_t Ms,
-                       const double* Xs, int64_t ldxs, double noise_s) {
-    int rc = sparse_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs);
-    if (rc) return rc;
-    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
-        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
-    return 0;
-}
-
 // The three stages of gaplac_sparse_posterior_mean_var (the mean in ctx->pmean, by the same
 // launches), then the augmented matrix of Sigma* into ctx->C, laid out for a factorisation of
 // order Ms with R riding responses (mirror: mirrored into a full matrix). tp comes in with the
@@ -2452,124 +2314,164 @@ int sparse_joint_stages(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, 
     });
 }
 
-int sparse_posterior_mean_cov_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                                   const gaplac_term* terms, double noise, const double* y, int64_t Mz,
-                                   const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
-                                   int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
-    if (!ctx) return GAPLAC_E_ARG;
-    if (Ms < 0 || (out_cov && ldc < Ms)) return set_err(ctx, GAPLAC_E_ARG, "Ms = %lld < 0 or ldc < Ms", (long long)Ms);
-    for (int64_t j = 0; j < Ms; ++j) {  // (rows Ms .. ldc-1 of out_cov are the caller's)
+// ---- the joint entries of both models (§10.6, §10.11), written once ----
+// The model of a joint call, in the entries' argument order: exact, or `sparse` (inducing points).
+struct JointModel {
+    int64_t N;
+    int32_t D;
+    const double* X;
+    int64_t ldx;
+    int32_t T;
+    const gaplac_term* terms;
+    double noise;
+    const double* y;
+    bool sparse = false;
+    int64_t Mz = 0;
+    const double* Z = nullptr;
+    int64_t ldz = 0;
+    double jitter = 0.0;
+    bool no_data() const { return N == 0 || (sparse && Mz == 0); }  // (or Q = 0): the posterior is the prior
+    const char* m_name() const { return sparse ? "Ms" : "M"; }       // in the error texts
+};
+
+// The checks the three entries share, after their own (sizes and output pointers), and the pack.
+int joint_check(gaplac_ctx* ctx, const JointModel& m, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                TermPack* tp) {
+    int rc = m.sparse ? sparse_check(ctx, m.N, m.D, m.X, m.ldx, m.noise, m.y, m.Mz, m.Z, m.ldz, m.jitter, M, Xs, ldxs)
+                      : check_common(ctx, m.N, m.D, m.X, m.ldx, m.noise, m.y);
+    if (rc) return rc;
+    if (!m.sparse && M > 0 && m.D > 0 && (!Xs || ldxs < M)) return set_err(ctx, GAPLAC_E_ARG, "Xs NULL or ldxs < M");
+    if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
+        return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
+    return pack_terms(ctx, m.D, m.T, m.terms, tp);
+}
+
+// The model's stages up to Sigma*, laid out for a factorisation of order M with R riding responses, in
+// ctx->B (the sparse entries: their third workspace, ctx->C). tp leaves with noise_s.
+int joint_model_stages(gaplac_ctx* ctx, const JointModel& m, TermPack& tp, int64_t M, const double* Xs, int64_t ldxs,
+                       double noise_s, int64_t R, Cov cov) {
+    tp.noise = m.noise;
+    if (!m.sparse) return joint_stages(ctx, m.N, m.D, m.X, m.ldx, tp, m.y, M, Xs, ldxs, noise_s, R, cov);
+    return sparse_joint_stages(ctx, m.N, m.D, m.X, m.ldx, tp, m.y, m.Mz, m.Z, m.ldz, m.jitter, M, Xs, ldxs, noise_s, R,
+                               cov == Cov::full);
+}
+
+// NaN into out_mean and the M x M block of out_cov (rows M .. ldc-1 are the caller's), where given.
+void nan_mean_cov(int64_t M, double* out_mean, double* out_cov, int64_t ldc) {
+    for (int64_t j = 0; j < M; ++j) {
         if (out_mean) out_mean[j] = NAN;
         if (out_cov)
-            for (int64_t i = 0; i < Ms; ++i) out_cov[j * ldc + i] = NAN;
+            for (int64_t i = 0; i < M; ++i) out_cov[j * ldc + i] = NAN;
     }
-    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
-    if (rc) return rc;
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (Ms == 0) return 0;
-    if (N == 0 || Mz == 0) {  // no data, or Q = 0: the prior
-        if (out_cov && (rc = gaplac_gram(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, out_cov, ldc))) return rc;
-        for (int64_t j = 0; j < Ms && out_mean; ++j) out_mean[j] = 0.0;
-        return 0;
-    }
-    tp.noise = noise;
-    if (!out_cov) {  // the mean alone: the three stages of gaplac_sparse_posterior_mean_var
-        return sparse_posterior_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, out_mean,
-                                     nullptr);
-    }
-    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, 0, true)))
-        return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->C, (size_t)sparse_joint_dims(Ms, 0).ldc * 8,
-                                (size_t)Ms * 8, (size_t)Ms, hipMemcpyDeviceToHost, ctx->s_main));
-    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, ctx->pmean, (size_t)Ms * 8, hipMemcpyDeviceToHost, ctx->s_main));
+}
+// The prior at the test points: its covariance by gaplac_gram and a zero mean.
+int prior_mean_cov(gaplac_ctx* ctx, int32_t D, int32_t T, const gaplac_term* terms, int64_t M, const double* Xs,
+                   int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
+    int rc;
+    if (out_cov && (rc = gaplac_gram(ctx, M, D, Xs, ldxs, T, terms, noise_s, out_cov, ldc))) return rc;
+    for (int64_t j = 0; j < M && out_mean; ++j) out_mean[j] = 0.0;
+    return 0;
+}
+// The covariance (the M x M block of dcov, ld ldd) and the mean read back; s_main has retired on return.
+int read_mean_cov(gaplac_ctx* ctx, int64_t M, const double* dcov, int64_t ldd, const double* dmean, double* out_mean,
+                  double* out_cov, int64_t ldc) {
+    if (out_cov)
+        HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, dcov, (size_t)ldd * 8, (size_t)M * 8, (size_t)M,
+                                    hipMemcpyDeviceToHost, ctx->s_main));
+    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, dmean, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
     return 0;
 }
 
-int sparse_posterior_rand_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                               const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
-                               int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs, double noise_s,
-                               int64_t R, const double* E, int64_t lde, double* out, int64_t ldo) {
+// gaplac_posterior_mean_cov and gaplac_sparse_posterior_mean_cov.
+int joint_mean_cov(gaplac_ctx* ctx, const JointModel& m, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                   double* out_mean, double* out_cov, int64_t ldc) {
     if (!ctx) return GAPLAC_E_ARG;
-    if (Ms < 0 || R < 0 || !out || lde < Ms || ldo < Ms || (R > 0 && Ms > 0 && !E))
-        return set_err(ctx, GAPLAC_E_ARG, "Ms < 0, R < 0, E / out NULL, or lde / ldo < Ms");
-    for (int64_t r = 0; r < R; ++r)  // (rows Ms .. ldo-1 of out are the caller's)
-        for (int64_t i = 0; i < Ms; ++i) out[r * ldo + i] = NAN;
-    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
-    if (rc) return rc;
+    if (M < 0 || (out_cov && ldc < M))
+        return set_err(ctx, GAPLAC_E_ARG, "%s = %lld < 0 or ldc < %s", m.m_name(), (long long)M, m.m_name());
+    nan_mean_cov(M, out_mean, out_cov, ldc);
     TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (Ms == 0 || R == 0) return 0;
-    if (N == 0 || Mz == 0)  // the prior at the test points
-        return gaplac_rand_multi(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, R, E, lde, out, ldo);
-    if ((R + NB - 1) / NB > 65535)
+    int rc = joint_check(ctx, m, M, Xs, ldxs, noise_s, &tp);
+    if (rc || M == 0) return rc;
+    if (m.no_data()) return prior_mean_cov(ctx, m.D, m.T, m.terms, M, Xs, ldxs, noise_s, out_mean, out_cov, ldc);
+    if (m.sparse && !out_cov)  // the mean alone: the three stages of gaplac_sparse_posterior_mean_var
+        return sparse_posterior_impl(ctx, m.N, m.D, m.X, m.ldx, m.T, m.terms, m.noise, m.y, m.Mz, m.Z, m.ldz, m.jitter,
+                                     M, Xs, ldxs, out_mean, nullptr);
+    if ((rc = joint_model_stages(ctx, m, tp, M, Xs, ldxs, noise_s, 0, out_cov ? Cov::full : Cov::none))) return rc;
+    return read_mean_cov(ctx, M, m.sparse ? ctx->C : ctx->B, round_up(M + 1, NB), ctx->pmean, out_mean, out_cov, ldc);
+}
+
+// gaplac_posterior_rand and gaplac_sparse_posterior_rand (which calls its Z "E"): out = m 1^T + L* Z.
+int joint_rand(gaplac_ctx* ctx, const JointModel& m, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+               int64_t R, const double* Z, int64_t ldz, double* out, int64_t ldo) {
+    if (!ctx) return GAPLAC_E_ARG;
+    if (M < 0 || R < 0 || !out || ldz < M || ldo < M || (R > 0 && M > 0 && !Z))
+        return set_err(ctx, GAPLAC_E_ARG, "%s < 0, R < 0, %s / out NULL, or %s / ldo < %s", m.m_name(),
+                       m.sparse ? "E" : "Z", m.sparse ? "lde" : "ldz", m.m_name());
+    for (int64_t r = 0; r < R; ++r)  // (rows M .. ldo-1 of out are the caller's)
+        for (int64_t i = 0; i < M; ++i) out[r * ldo + i] = NAN;
+    TermPack tp;
+    int rc = joint_check(ctx, m, M, Xs, ldxs, noise_s, &tp);
+    if (rc || M == 0 || R == 0) return rc;
+    if (m.no_data())  // the prior at the test points
+        return gaplac_rand_multi(ctx, M, m.D, Xs, ldxs, m.T, m.terms, noise_s, R, Z, ldz, out, ldo);
+    if (m.sparse && (R + NB - 1) / NB > 65535)  // (the sparse entry alone: the exact one takes any R)
         return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
-    tp.noise = noise;
-    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, 0, false)))
-        return rc;
-    const int64_t Msp = sparse_joint_dims(Ms, 0).Msp;
-    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Msp * (size_t)R))) return rc;
-    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)Ms * (size_t)R))) return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Msp * 8, E, (size_t)lde * 8, (size_t)Ms * 8, (size_t)R,
+    if ((rc = joint_model_stages(ctx, m, tp, M, Xs, ldxs, noise_s, 0, Cov::lower))) return rc;
+    const int64_t Mp = round_up(M + 1, NB);
+    if ((rc = ensure(ctx, &ctx->dZ, &ctx->dZ_elems, (size_t)Mp * (size_t)R))) return rc;
+    if ((rc = ensure(ctx, &ctx->dO, &ctx->dO_elems, (size_t)M * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dZ, (size_t)Mp * 8, Z, (size_t)ldz * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyHostToDevice, ctx->s_main));
-    WsSwap third(ctx, &ctx->C, &ctx->C_elems);  // from here on ctx->A is the order-Ms workspace
-    EvalResult r3;
-    if ((rc = joint_factor(ctx, Ms, D, tp, ExtraRows{}.on_prebuilt(), &r3))) return rc;
-    if ((rc = guarded(ctx, false,
-                      [&] { draws_launches(ctx->s_main, ctx->A, Msp, Ms, ctx->dZ, R, ctx->dO, ctx->pmean); })))
+    WsSwap swap(ctx, m.sparse ? &ctx->C : &ctx->B, m.sparse ? &ctx->C_elems : &ctx->B_elems);  // ctx->A: order M
+    EvalResult r;
+    if ((rc = joint_factor(ctx, M, m.D, tp, ExtraRows{}.on_prebuilt(), &r))) return rc;
+    if ((rc = guarded(ctx, false, [&] { draws_launches(ctx->s_main, ctx->A, Mp, M, ctx->dZ, R, ctx->dO, ctx->pmean); })))
         return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)Ms * 8, (size_t)Ms * 8, (size_t)R,
+    HIPCK(ctx, hipMemcpy2DAsync(out, (size_t)ldo * 8, ctx->dO, (size_t)M * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyDeviceToHost, ctx->s_main));
     HIPCK(ctx, hipStreamSynchronize(ctx->s_main));
     return 0;
 }
 
-int sparse_posterior_logpdf_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                                 const gaplac_term* terms, double noise, const double* y, int64_t Mz,
-                                 const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
-                                 int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
-                                 double* out_logpdf, double* out_logdet, double* out_quad) {
+// gaplac_posterior_logpdf and gaplac_sparse_posterior_logpdf: every column of Ys under the joint posterior.
+int joint_logpdf(gaplac_ctx* ctx, const JointModel& m, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                 int64_t R, const double* Ys, int64_t ldys, double* out_logpdf, double* out_logdet, double* out_quad) {
     if (!ctx) return GAPLAC_E_ARG;
-    if (Ms < 0 || R < 0 || !out_logpdf || ldys < Ms || (R > 0 && Ms > 0 && !Ys))
-        return set_err(ctx, GAPLAC_E_ARG, "Ms < 0, R < 0, Ys / out_logpdf NULL, or ldys < Ms");
-    if (Ms > 0 && R > 0) {  // (an empty call writes nothing)
+    if (M < 0 || R < 0 || !out_logpdf || ldys < M || (R > 0 && M > 0 && !Ys))
+        return set_err(ctx, GAPLAC_E_ARG, "%s < 0, R < 0, Ys / out_logpdf NULL, or ldys < %s", m.m_name(), m.m_name());
+    if (M > 0 && R > 0) {  // (an empty call writes nothing)
         for (int64_t r = 0; r < R; ++r) {
             out_logpdf[r] = NAN;
             if (out_quad) out_quad[r] = NAN;
         }
         if (out_logdet) *out_logdet = NAN;
     }
-    int rc = sparse_joint_check(ctx, N, D, X, ldx, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s);
-    if (rc) return rc;
     TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    if (Ms == 0 || R == 0) return 0;
-    if (N == 0 || Mz == 0)  // the prior at the test points
-        return gaplac_logpdf_multi(ctx, Ms, D, Xs, ldxs, T, terms, noise_s, R, Ys, ldys, out_logpdf, out_logdet,
+    int rc = joint_check(ctx, m, M, Xs, ldxs, noise_s, &tp);
+    if (rc || M == 0 || R == 0) return rc;
+    if (m.no_data())  // the prior at the test points
+        return gaplac_logpdf_multi(ctx, M, m.D, Xs, ldxs, m.T, m.terms, noise_s, R, Ys, ldys, out_logpdf, out_logdet,
                                    out_quad);
     if ((R + NB - 1) / NB > 65535)  // (one grid row of the transposing launch per tile row)
         return set_err(ctx, GAPLAC_E_OOM, "R = %lld: more than 65535 tile rows in one call", (long long)R);
-    tp.noise = noise;
-    if ((rc = sparse_joint_stages(ctx, N, D, X, ldx, tp, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s, R, false)))
-        return rc;
-    // ctx->dY held the transposed a rows for stage 3, which has retired: the responses take it over
-    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)Ms * (size_t)R))) return rc;
-    HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)Ms * 8, Ys, (size_t)ldys * 8, (size_t)Ms * 8, (size_t)R,
+    if ((rc = joint_model_stages(ctx, m, tp, M, Xs, ldxs, noise_s, R, Cov::lower))) return rc;
+    // (sparse: ctx->dY held the transposed a rows for stage 3, which has retired: the responses take it over)
+    if ((rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)M * (size_t)R))) return rc;
+    HIPCK(ctx, hipMemcpy2DAsync(ctx->dY, (size_t)M * 8, Ys, (size_t)ldys * 8, (size_t)M * 8, (size_t)R,
                                 hipMemcpyHostToDevice, ctx->s_main));
-    WsSwap third(ctx, &ctx->C, &ctx->C_elems);
+    WsSwap swap(ctx, m.sparse ? &ctx->C : &ctx->B, m.sparse ? &ctx->C_elems : &ctx->B_elems);
     // the rows hold (Ys - m 1^T)^T and ride along as the responses of gaplac_logpdf_multi do
-    EvalResult r3;
-    if ((rc = joint_factor(ctx, Ms, D, tp, ExtraRows::responses(R, ctx->dY, Ms, ctx->pmean).on_prebuilt(), &r3)))
+    EvalResult r;
+    if ((rc = joint_factor(ctx, M, m.D, tp, ExtraRows::responses(R, ctx->dY, M, ctx->pmean).on_prebuilt(), &r)))
         return rc;
-    if (out_logdet) *out_logdet = r3.logdet;
+    if (out_logdet) *out_logdet = r.logdet;
     if (out_quad) HIPCK(ctx, hipMemcpy(out_quad, ctx->mres, (size_t)R * 8, hipMemcpyDeviceToHost));
     HIPCK(ctx, hipMemcpy(out_logpdf, ctx->mres + R, (size_t)R * 8, hipMemcpyDeviceToHost));
     return 0;
 }
 
 }  // namespace
-
 
 // Batched tail: models m0 .. m0+B-1 of a select batch whose matrix lies
 // whole in the persistent tail, evaluated together on workspace set p: the Grams and
@@ -2740,6 +2642,67 @@ static int dry_walk(gaplac_ctx& c, int64_t N, const ExtraRows& xr, LaunchGuard& 
     return rc;
 }
 
+// What every gaplac_plan_check_* entry is written on: the fake regions, the entries'
+// own *_launches functions run under a dry guard, the dry evaluations between them, and the report.
+// Launches and violations add up; `first` is the first violation in walk order. After an evaluation
+// fails for another reason than a violation the walk does nothing more and report() returns that code.
+namespace {
+struct PlanWalk {
+    int spw;
+    int rc = 0;
+    int64_t launches = 0, violations = 0;
+    std::string first;
+    const LaunchGuard* open = nullptr;  // the evaluation whose `after` is running
+
+    // The never-dereferenced base of fake region k. An evaluation's workspace is region 0 (dry_walk).
+    static double* region(int k) { return reinterpret_cast<double*>((uintptr_t)1 << (44 + k)); }
+
+    void note(const LaunchGuard& g) { if (first.empty() && g.violations) first = g.first; }
+    void add(const LaunchGuard& g) {
+        launches += g.launches;
+        violations += g.violations;
+        note(g);
+    }
+    // `run` under a fresh dry guard over up to three regions, in guarded_on's shape.
+    template <typename Launches>
+    void on(const double* base, int64_t elems, const double* base2, int64_t elems2, Launches&& run,
+            const double* base3 = nullptr, int64_t elems3 = 0) {
+        if (rc) return;
+        if (open) note(*open);  // (inside an evaluation: what that has found so far came first)
+        LaunchGuard g{base, elems, base2, elems2, base3, elems3, /*dry*/ true};
+        {
+            GuardScope scope(&g);
+            run();
+        }
+        add(g);
+    }
+    // One evaluation of order N with the rows xr, walked dry in a context of its own whose
+    // workspace is short_by elements short; base2: a second region for the launches of `after`.
+    // GAPLAC_E_ARG with violations is the walk's finding, reported in the counts, not a failure.
+    void eval(int64_t N, const ExtraRows& xr, int64_t short_by = 0,
+              const std::function<int(gaplac_ctx&)>& after = nullptr, const double* base2 = nullptr,
+              int64_t elems2 = 0) {
+        if (rc) return;
+        gaplac_ctx c;
+        c.spw = spw;
+        LaunchGuard g;
+        g.base2 = base2;
+        g.elems2 = elems2;
+        open = &g;
+        rc = dry_walk(c, N, xr, g, short_by, after);
+        open = nullptr;
+        if (rc == GAPLAC_E_ARG && g.violations) rc = 0;
+        add(g);
+    }
+    int report(int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) const {
+        if (out_launches) *out_launches = launches;
+        if (out_violations) *out_violations = violations;
+        if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
+        return rc;
+    }
+};
+}  // namespace
+
 // ---------------------------------------------------------------------------------
 // Fitted posterior: one factorisation kept, queried many times.
 // ---------------------------------------------------------------------------------
@@ -2847,8 +2810,9 @@ static void fit_unregister(gaplac_fit* f) {
     f->ctx = nullptr;
 }
 
-static int fit_create_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                           const gaplac_term* terms, double noise, const double* y, int64_t cap, gaplac_fit** out) {
+extern "C" int gaplac_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
+                                 const gaplac_term* terms, double noise, const double* y, int64_t cap,
+                                 gaplac_fit** out) {
     if (!out) return ctx ? set_err(ctx, GAPLAC_E_ARG, "out is NULL") : GAPLAC_E_ARG;
     *out = nullptr;
     int rc = check_common(ctx, N, D, X, ldx, noise, y);
@@ -2930,7 +2894,7 @@ static int fit_upload_xs(gaplac_fit* f, int64_t r0, int64_t m, const double* Xs,
     return 0;
 }
 
-static int fit_mean_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean) {
+extern "C" int gaplac_fit_mean(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean) {
     for (int64_t j = 0; out_mean && j < M; ++j) out_mean[j] = NAN;
     int rc = fit_query_check(f, M, Xs, ldxs);
     if (rc) return rc > 0 ? 0 : rc;
@@ -2954,9 +2918,9 @@ static int fit_mean_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldx
     return 0;
 }
 
-static int fit_mean_var_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
-                             double* out_var) {
-    if (!out_var) return fit_mean_impl(f, M, Xs, ldxs, out_mean);
+extern "C" int gaplac_fit_mean_var(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
+                                   double* out_var) {
+    if (!out_var) return gaplac_fit_mean(f, M, Xs, ldxs, out_mean);
     for (int64_t j = 0; j < M; ++j) {
         if (out_mean) out_mean[j] = NAN;
         out_var[j] = NAN;
@@ -2989,17 +2953,13 @@ static int fit_mean_var_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t
 
 // The joint covariance of M <= cap test points from a fit of either kind (§10.15): the query's rows
 // and mean, then launch_post_cov + launch_mirror_lower reading the rows from the fit's buffer.
-static int fit_mean_cov_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
-                             double* out_mean, double* out_cov, int64_t ldc) {
+extern "C" int gaplac_fit_mean_cov(gaplac_fit* f, int64_t M, const double* Xs, int64_t ldxs, double noise_s,
+                                   double* out_mean, double* out_cov, int64_t ldc) {
     if (!f || !f->ctx) return GAPLAC_E_ARG;
     gaplac_ctx* ctx = f->ctx;
     if (M < 0 || (out_cov && ldc < M))
         return set_err(ctx, GAPLAC_E_ARG, "M = %lld < 0 or ldc %lld < M", (long long)M, (long long)ldc);
-    for (int64_t j = 0; j < M; ++j) {  // (rows M .. ldc-1 of out_cov are the caller's)
-        if (out_mean) out_mean[j] = NAN;
-        if (out_cov)
-            for (int64_t i = 0; i < M; ++i) out_cov[j * ldc + i] = NAN;
-    }
+    nan_mean_cov(M, out_mean, out_cov, ldc);
     if (M > f->cap)
         return set_err(ctx, GAPLAC_E_ARG, "M = %lld > cap = %lld: the joint covariance takes one chunk of test points",
                        (long long)M, (long long)f->cap);
@@ -3008,13 +2968,10 @@ static int fit_mean_cov_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t
     if (!(noise_s >= 0.0) || !std::isfinite(noise_s))
         return set_err(ctx, GAPLAC_E_ARG, "noise_s %g must be finite and >= 0", noise_s);
     if (rc > 0) return 0;
-    if (!out_cov) return fit_mean_impl(f, M, Xs, ldxs, out_mean);
-    if (f->N == 0) {  // the prior
-        if ((rc = gaplac_gram(ctx, M, f->D, Xs, ldxs, (int32_t)f->terms.size(), f->terms.data(), noise_s, out_cov, ldc)))
-            return rc;
-        for (int64_t j = 0; j < M && out_mean; ++j) out_mean[j] = 0.0;
-        return 0;
-    }
+    if (!out_cov) return gaplac_fit_mean(f, M, Xs, ldxs, out_mean);
+    if (f->N == 0)  // the prior
+        return prior_mean_cov(ctx, f->D, (int32_t)f->terms.size(), f->terms.data(), M, Xs, ldxs, noise_s, out_mean,
+                              out_cov, ldc);
     HIPCK(ctx, hipSetDevice(f->device));
     const FitDims& d = f->d;
     hipStream_t s = ctx->s_main;
@@ -3032,11 +2989,7 @@ static int fit_mean_cov_impl(gaplac_fit* f, int64_t M, const double* Xs, int64_t
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    HIPCK(ctx, hipMemcpy2DAsync(out_cov, (size_t)ldc * 8, ctx->B, (size_t)ldb * 8, (size_t)M * 8, (size_t)M,
-                                hipMemcpyDeviceToHost, s));
-    if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean, f->buf + d.mean, (size_t)M * 8, hipMemcpyDeviceToHost, s));
-    HIPCK(ctx, hipStreamSynchronize(s));
-    return 0;
+    return read_mean_cov(ctx, M, ctx->B, ldb, f->buf + d.mean, out_mean, out_cov, ldc);
 }
 
 // ---------------------------------------------------------------------------------
@@ -3216,38 +3169,54 @@ static int lap_bad_w(gaplac_ctx* ctx, int64_t N, double count, int64_t* out_info
                            "observations (exp(f) overflows)", (long long)N, count);
 }
 
-// The outputs of gaplac_laplace_logpdf_grad (each may be NULL).
-struct LapGradOut {
-    double* dparam;    // T
-    double* djitter;
-    double* implicit;  // T + 1
-};
-
-// gaplac_laplace_fit_create's request (§10.15): after the final factorisation a fit of kind 1 is
-// filled from the workspace and the vectors and handed out through *out.
-struct LapFitOut {
-    int64_t cap;
-    gaplac_fit** out;
-};
-
-// The handle of a Laplace fit before its buffer is filled (all of it for N = 0).
-static std::unique_ptr<gaplac_fit> lap_fit_new(gaplac_ctx* ctx, int64_t N, int32_t D, int32_t T,
-                                               const gaplac_term* terms, const TermPack& tp, int64_t cap, int32_t lik,
-                                               double lik_param, double jitter) {
-    std::unique_ptr<gaplac_fit> f(new gaplac_fit());
-    f->device = ctx->device;
-    f->N = N;
-    f->cap = cap;
-    f->D = D;
-    f->tp = tp;
-    f->tp.noise = jitter;
-    f->terms.assign(terms, terms + T);
-    f->kind = 1;
-    f->lik = lik;
-    f->lik_param = lik_param;
-    f->jitter = jitter;
-    return f;
+static int lap_bad_b(gaplac_ctx* ctx, int64_t N, int info, int64_t* out_info) {
+    if (out_info) *out_info = info;
+    return set_err(ctx, info, "B = I + sqrt(W) K sqrt(W) (order %lld): its Cholesky factorisation failed at leading "
+                              "minor %d, which an indefinite matrix cannot cause (B >= I): W or K is not finite",
+                   (long long)N, info);
 }
+
+namespace {
+// What a Laplace entry is asked, in the entries' argument order (a0 may be NULL; M = 0: no test points).
+struct LapRequest {
+    int64_t N;
+    int32_t D;
+    const double* X;
+    int64_t ldx;
+    int32_t T;
+    const gaplac_term* terms;
+    double jitter;
+    int32_t lik;
+    double lik_param;
+    const double* y;
+    int32_t max_iter;
+    double tol;
+    const double* a0;
+    int64_t M;
+    const double* Xs;
+    int64_t ldxs;
+};
+
+// What it may answer (every pointer but logq may be NULL): what all four entries have, first.
+struct LapOut {
+    double* logq;
+    int32_t *iters, *converged;
+    int64_t* info;
+    double *f, *a;       // the mode and a = K^{-1} f, N values each
+    double *mean, *var;  // at the M test points
+    // gaplac_laplace_logpdf_grad (§10.14): the final factorisation carries identity rows
+    bool grad;
+    double *dparam, *djitter, *implicit;  // T, 1 and T + 1 values
+    // gaplac_laplace_fit_create (§10.15): a fit of kind 1 with room for cap test points, out through *fit
+    gaplac_fit** fit;
+    int64_t cap;
+};
+
+struct LapResult {  // what the iteration and the final factorisation leave for the answer
+    double logq, logdet, atf;
+    int iters;
+    bool converged;
+};
 
 // The create-time launches of a Laplace fit after the final factorisation: the factor's lower tiles
 // out of the workspace A (ld Np) and sw, f, a out of the vectors' buffer (alpha, the buffer's last
@@ -3260,7 +3229,7 @@ static void lap_fit_create_launches(hipStream_t s, const FitDims& d, const LapDi
 
 // The buffer of a Laplace fit out of the context after the final factorisation of B (ld Np in the
 // workspace, M = 0, no identity rows): the factor's lower tiles, Dinv, X and the pack as
-// fit_create_impl copies them, and sw, f, a out of the vectors' buffer.
+// gaplac_fit_create copies them, and sw, f, a out of the vectors' buffer.
 static int lap_fit_fill(gaplac_ctx* ctx, gaplac_fit* f, const LapDims& ld) {
     const int64_t N = f->N;
     f->d = fit_dims(N, f->D, f->cap, true);
@@ -3295,250 +3264,329 @@ static int lap_fit_fill(gaplac_ctx* ctx, gaplac_fit* f, const LapDims& ld) {
     return 0;
 }
 
-// Shared body of gaplac_laplace_logpdf (M = 0, no test outputs), gaplac_laplace_posterior_mean_var,
-// gaplac_laplace_logpdf_grad (grad: M = 0, the final factorisation carries identity rows) and
-// gaplac_laplace_fit_create (fit: M = 0, the factor and the vectors are kept in a gaplac_fit).
-static int laplace_impl(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                        const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
-                        int32_t max_iter, double tol, const double* a0, bool posterior, int64_t M, const double* Xs,
-                        int64_t ldxs, double* out_logq, double* out_f, double* out_a, double* out_mean,
-                        double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info,
-                        const LapGradOut* grad = nullptr, const LapFitOut* fit = nullptr) {
-    if (out_logq) *out_logq = NAN;
-    if (grad) {
-        if (grad->djitter) *grad->djitter = NAN;
-        for (int t = 0; t < T && t < GAPLAC_MAX_TERMS; ++t)
-            if (grad->dparam) grad->dparam[t] = NAN;
-        for (int t = 0; t <= T && t <= GAPLAC_MAX_TERMS; ++t)
-            if (grad->implicit) grad->implicit[t] = NAN;
-    }
-    if (out_iters) *out_iters = 0;
-    if (out_converged) *out_converged = 0;
-    if (out_info) *out_info = 0;
-    for (int64_t i = 0; i < N; ++i) {
-        if (out_f) out_f[i] = NAN;
-        if (out_a) out_a[i] = NAN;
-    }
-    for (int64_t j = 0; posterior && j < M; ++j) {
-        if (out_mean) out_mean[j] = NAN;
-        if (out_var) out_var[j] = NAN;
-    }
-    int rc = check_common(ctx, N, D, X, ldx, 0.0, y);
+// The handle of a finished call, registered with the context and handed out through *o.fit: the
+// empty fit (d null, N = 0: the prior at every query), or the one filled by lap_fit_fill.
+static int lap_fit_hand_out(gaplac_ctx* ctx, const LapRequest& q, const LapOut& o, const TermPack& tp,
+                            const LapDims* d, const LapResult& res) {
+    std::unique_ptr<gaplac_fit> f(new gaplac_fit());
+    f->device = ctx->device;
+    f->N = q.N;
+    f->cap = o.cap;
+    f->D = q.D;
+    f->tp = tp;
+    f->tp.noise = q.jitter;
+    f->terms.assign(q.terms, q.terms + q.T);
+    f->kind = 1;
+    f->lik = q.lik;
+    f->lik_param = q.lik_param;
+    f->jitter = q.jitter;
+    f->logpdf = res.logq;
+    f->logdet = res.logdet;
+    f->quad = res.atf;
+    f->iters = res.iters;
+    f->converged = res.converged ? 1 : 0;
+    int rc;
+    if (d && (rc = lap_fit_fill(ctx, f.get(), *d))) return rc;
+    f->ctx = ctx;
+    ctx->fits.push_back(f.get());
+    *o.fit = f.release();
+    return 0;
+}
+
+// v into every value the entry may write, 0 into its counters: NaN before any check, 0 without observations.
+static void lap_fill_out(const LapRequest& q, const LapOut& o, double v) {
+    if (o.logq) *o.logq = v;
+    if (o.djitter) *o.djitter = v;
+    for (int t = 0; o.dparam && t < q.T && t < GAPLAC_MAX_TERMS; ++t) o.dparam[t] = v;
+    for (int t = 0; o.implicit && t <= q.T && t <= GAPLAC_MAX_TERMS; ++t) o.implicit[t] = v;
+    if (o.iters) *o.iters = 0;
+    if (o.converged) *o.converged = 0;
+    if (o.info) *o.info = 0;
+    for (double* p : {o.f, o.a})
+        for (int64_t i = 0; p && i < q.N; ++i) p[i] = v;
+    for (double* p : {o.mean, o.var})
+        for (int64_t j = 0; p && j < q.M; ++j) p[j] = v;
+}
+
+// Whether an observation v lies in the likelihood's support.
+static bool lik_supports(int lik, double v) {
+    return lik == GAPLAC_LIK_BERNOULLI ? (v == 0.0 || v == 1.0)
+           : lik == GAPLAC_LIK_POISSON ? (std::isfinite(v) && v >= 0.0 && v == std::floor(v))
+                                       : std::isfinite(v);
+}
+
+// The argument checks, the pack and the observations' support.
+static int lap_check(gaplac_ctx* ctx, const LapRequest& q, const LapOut& o, TermPack* tp) {
+    int rc = check_common(ctx, q.N, q.D, q.X, q.ldx, 0.0, q.y);
     if (rc) return rc;
-    if (posterior && (M < 0 || (M > 0 && D > 0 && (!Xs || ldxs < M))))
+    if (q.M < 0 || (q.M > 0 && q.D > 0 && (!q.Xs || q.ldxs < q.M)))
         return set_err(ctx, GAPLAC_E_ARG, "M < 0, or Xs NULL / ldxs < M");
-    if (!out_logq) return set_err(ctx, GAPLAC_E_ARG, "out_logq is NULL");
-    if (fit && fit->cap < 1) return set_err(ctx, GAPLAC_E_ARG, "cap = %lld < 1", (long long)fit->cap);
-    if (lik != GAPLAC_LIK_GAUSSIAN && lik != GAPLAC_LIK_BERNOULLI && lik != GAPLAC_LIK_POISSON)
-        return set_err(ctx, GAPLAC_E_KIND, "unknown likelihood %d", lik);
-    if (!(jitter >= 0.0) || !std::isfinite(jitter))
-        return set_err(ctx, GAPLAC_E_PARAM, "jitter %g must be finite and >= 0", jitter);
-    if (!(tol > 0.0) || !std::isfinite(tol)) return set_err(ctx, GAPLAC_E_PARAM, "tol %g must be finite and > 0", tol);
-    if (max_iter < 1) return set_err(ctx, GAPLAC_E_PARAM, "max_iter = %d < 1", max_iter);
-    if (lik == GAPLAC_LIK_GAUSSIAN && (!(lik_param > 0.0) || !std::isfinite(lik_param)))
-        return set_err(ctx, GAPLAC_E_PARAM, "the Gaussian likelihood's variance %g must be finite and > 0", lik_param);
-    TermPack tp;
-    if ((rc = pack_terms(ctx, D, T, terms, &tp))) return rc;
-    for (int64_t i = 0; i < N; ++i) {
-        const double v = y[i];
-        const bool ok = lik == GAPLAC_LIK_BERNOULLI ? (v == 0.0 || v == 1.0)
-                        : lik == GAPLAC_LIK_POISSON ? (std::isfinite(v) && v >= 0.0 && v == std::floor(v))
-                                                    : std::isfinite(v);
-        if (!ok)
-            return set_err(ctx, GAPLAC_E_PARAM, "y[%lld] = %g is outside the likelihood's support", (long long)i, v);
-    }
-    for (int64_t i = 0; a0 && i < N; ++i)
-        if (!std::isfinite(a0[i])) return set_err(ctx, GAPLAC_E_PARAM, "a0[%lld] is not finite", (long long)i);
-    if (N == 0) {  // no observations: log q = 0 and the prior at the test points
-        *out_logq = 0.0;
-        if (out_converged) *out_converged = 1;
-        if (grad) {
-            if (grad->djitter) *grad->djitter = 0.0;
-            for (int t = 0; t < T; ++t)
-                if (grad->dparam) grad->dparam[t] = 0.0;
-            for (int t = 0; t <= T; ++t)
-                if (grad->implicit) grad->implicit[t] = 0.0;
-        }
-        for (int64_t j = 0; posterior && j < M; ++j) {
-            if (out_mean) out_mean[j] = 0.0;
-            if (out_var) out_var[j] = host_kdiag(tp, Xs, ldxs, j);
-        }
-        if (fit) {  // the empty fit: the prior at every query
-            std::unique_ptr<gaplac_fit> f = lap_fit_new(ctx, 0, D, T, terms, tp, fit->cap, lik, lik_param, jitter);
-            f->logpdf = f->logdet = f->quad = 0.0;
-            f->converged = 1;
-            f->ctx = ctx;
-            ctx->fits.push_back(f.get());
-            *fit->out = f.release();
-        }
-        return 0;
-    }
-    tp.noise = jitter;
-    if (!posterior) M = 0;
-    const LapDims d = lap_dims(N, M, grad != nullptr);
-    if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535 || (fit && (fit->cap + NB - 1) / NB > 65535))
-        return set_err(ctx, GAPLAC_E_OOM, "more than 65535 tile rows in one call");
+    if (!o.logq) return set_err(ctx, GAPLAC_E_ARG, "out_logq is NULL");
+    if (o.fit && o.cap < 1) return set_err(ctx, GAPLAC_E_ARG, "cap = %lld < 1", (long long)o.cap);
+    if (q.lik != GAPLAC_LIK_GAUSSIAN && q.lik != GAPLAC_LIK_BERNOULLI && q.lik != GAPLAC_LIK_POISSON)
+        return set_err(ctx, GAPLAC_E_KIND, "unknown likelihood %d", q.lik);
+    if (!(q.jitter >= 0.0) || !std::isfinite(q.jitter))
+        return set_err(ctx, GAPLAC_E_PARAM, "jitter %g must be finite and >= 0", q.jitter);
+    if (!(q.tol > 0.0) || !std::isfinite(q.tol))
+        return set_err(ctx, GAPLAC_E_PARAM, "tol %g must be finite and > 0", q.tol);
+    if (q.max_iter < 1) return set_err(ctx, GAPLAC_E_PARAM, "max_iter = %d < 1", q.max_iter);
+    if (q.lik == GAPLAC_LIK_GAUSSIAN && (!(q.lik_param > 0.0) || !std::isfinite(q.lik_param)))
+        return set_err(ctx, GAPLAC_E_PARAM, "the Gaussian likelihood's variance %g must be finite and > 0", q.lik_param);
+    if ((rc = pack_terms(ctx, q.D, q.T, q.terms, tp))) return rc;
+    for (int64_t i = 0; i < q.N; ++i)
+        if (!lik_supports(q.lik, q.y[i]))
+            return set_err(ctx, GAPLAC_E_PARAM, "y[%lld] = %g is outside the likelihood's support", (long long)i, q.y[i]);
+    for (int64_t i = 0; q.a0 && i < q.N; ++i)
+        if (!std::isfinite(q.a0[i])) return set_err(ctx, GAPLAC_E_PARAM, "a0[%lld] is not finite", (long long)i);
+    return 0;
+}
+
+// The inputs, the buffers and the packs onto the device, K's diagonal part, and the start:
+// a = a0 and f = K a, or both 0. *singletons: the gradient's groups are single terms.
+static int lap_upload(gaplac_ctx* ctx, const LapRequest& q, const LapDims& d, const TermPack& tp, bool grad,
+                      bool* singletons) {
+    int rc;
+    const int64_t N = q.N;
     HIPCK(ctx, hipSetDevice(ctx->device));
-    if ((rc = upload(ctx, N, D, X, ldx, y))) return rc;
+    if ((rc = upload(ctx, N, q.D, q.X, q.ldx, q.y))) return rc;
     if ((rc = ensure(ctx, &ctx->A, &ctx->A_elems, (size_t)d.a_elems))) return rc;
     if ((rc = ensure(ctx, &ctx->lap, &ctx->lap_elems, (size_t)d.elems))) return rc;
     if (d.qc > 0 && (rc = ensure(ctx, &ctx->dY, &ctx->dY_elems, (size_t)N * (size_t)d.qc))) return rc;
     hipStream_t s = ctx->s_main;
     double* const lap = ctx->lap;
-    const double* const dy = ctx->dv;
     *ctx->htp = tp;
     HIPCK(ctx, hipMemcpyAsync(ctx->dtp, ctx->htp, sizeof(TermPack), hipMemcpyHostToDevice, s));
-    bool singletons = true;
     if (grad) {  // the product groups' bounds, as gaplac_logpdf_grad packs them
         GradTermPack gp{};
-        singletons = pack_groups(T, terms, &gp);
+        *singletons = pack_groups(q.T, q.terms, &gp);
         *ctx->hgp = gp;
         HIPCK(ctx, hipMemcpyAsync(ctx->dgp, ctx->hgp, sizeof(GradTermPack), hipMemcpyHostToDevice, s));
     }
     {
         std::vector<double> diag((size_t)N);
-        for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = jitter + host_noise_diag(tp, X, ldx, i);
+        for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = q.jitter + host_noise_diag(tp, q.X, q.ldx, i);
         HIPCK(ctx, hipMemcpyAsync(lap + d.diag, diag.data(), (size_t)N * 8, hipMemcpyHostToDevice, s));
         HIPCK(ctx, hipStreamSynchronize(s));  // (diag is the host's: it ends with this block)
     }
-    // a = a0 and f = K a, or both 0
-    if (a0) {
-        HIPCK(ctx, hipMemcpyAsync(lap + d.a, a0, (size_t)N * 8, hipMemcpyHostToDevice, s));
-        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.a, d.f); })))
-            return rc;
-        if ((rc = lap_on_ws(ctx, [&] { launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.a, lap + d.f); }))) return rc;
-    } else {
+    if (!q.a0) {
         HIPCK(ctx, hipMemsetAsync(lap + d.a, 0, (size_t)N * 8, s));
         HIPCK(ctx, hipMemsetAsync(lap + d.f, 0, (size_t)N * 8, s));
+        return 0;
     }
-    double h[4];
-    auto fail_b = [&](int info) {
-        if (out_info) *out_info = info;
-        return set_err(ctx, info, "B = I + sqrt(W) K sqrt(W) (order %lld): its Cholesky factorisation failed at leading "
-                                  "minor %d, which an indefinite matrix cannot cause (B >= I): W or K is not finite",
-                       (long long)N, info);
-    };
-    int iters = 0;
-    bool converged = false;
-    EvalResult r;
-    for (int it = 0; it < max_iter; ++it) {
-        // the likelihood at (a, f); c = K b; K and B; the factorisation
-        if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(s, d, N, lik, lik_param, dy, lap); }))) return rc;
-        if ((rc = lap_read_sums(ctx, d, h))) return rc;
-        if (h[3] > 0.0) return lap_bad_w(ctx, N, h[3], out_info);
-        const double psi_old = h[2];
-        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.b, d.c); })))
-            return rc;
-        if ((rc = lap_on_ws(ctx, [&] { lap_build_launches(s, d, N, d.Np, true, ctx->A, ctx->dX, dy, ctx->dtp, lap); })))
-            return rc;
-        if ((rc = eval_device(ctx, N, D, tp, ExtraRows{}.on_prebuilt(), &r))) return rc;
-        if ((rc = finish(r, nullptr, nullptr, nullptr))) return fail_b(rc);
-        // u = B^{-1} (sw c), a+ = b - sw u, f+ = K a+
-        if ((rc = lap_on_ws(ctx, [&] { lap_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
-        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.an, d.fn); })))
-            return rc;
-        if ((rc = lap_on_ws(ctx, [&] { lap_fnew_launches(s, d, N, lap); }))) return rc;
-        // the step: the first s = 1, 1/2, ... whose psi is finite and no worse than psi_old (to rounding)
-        double step = 1.0, psi_new = NAN;
-        bool accepted = false;
-        for (int hv = 0; hv <= 20 && !accepted; ++hv, step *= 0.5) {
-            if ((rc = lap_on_ws(ctx, [&] { lap_trial_launches(s, d, N, lik, lik_param, step, dy, lap); }))) return rc;
-            if ((rc = lap_read_sums(ctx, d, h))) return rc;
-            psi_new = h[2];
-            accepted = std::isfinite(psi_new) && psi_new >= psi_old - tol * (1.0 + std::fabs(psi_old));
-        }
-        if (!accepted) break;  // no acceptable step: the iterate stays, not converged
-        HIPCK(ctx, hipMemcpyAsync(lap + d.a, lap + d.at, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-        HIPCK(ctx, hipMemcpyAsync(lap + d.f, lap + d.ft, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
-        ++iters;
-        if (std::fabs(psi_new - psi_old) <= tol * (1.0 + std::fabs(psi_new))) {
-            converged = true;
-            break;
-        }
-    }
-    // W at the last iterate, B factored once more (with the first chunk of test points riding)
-    if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(s, d, N, lik, lik_param, dy, lap); }))) return rc;
+    HIPCK(ctx, hipMemcpyAsync(lap + d.a, q.a0, (size_t)N * 8, hipMemcpyHostToDevice, s));
+    if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.a, d.f); })))
+        return rc;
+    return lap_on_ws(ctx, [&] { launch_laplace_axpy_diag(s, N, lap + d.diag, lap + d.a, lap + d.f); });
+}
+
+// The likelihood at (a, f) and its sums h; W must be finite.
+static int lap_lik_at_iterate(gaplac_ctx* ctx, const LapRequest& q, const LapDims& d, int64_t* out_info, double* h) {
+    int rc;
+    if ((rc = lap_on_ws(ctx, [&] { lap_lik_launches(ctx->s_main, d, q.N, q.lik, q.lik_param, ctx->dv, ctx->lap); })))
+        return rc;
     if ((rc = lap_read_sums(ctx, d, h))) return rc;
-    if (h[3] > 0.0) return lap_bad_w(ctx, N, h[3], out_info);
-    const double psi = h[2], atf = h[1];
-    double logq = NAN;
-    std::vector<double> quad;
-    for (int64_t r0 = 0; r0 == 0 || r0 < M; r0 += LAP_CHUNK) {
-        const int64_t m = std::min(LAP_CHUNK, M - r0);
-        ExtraRows xr;
-        if (m > 0) {
-            const int64_t lda = d.Np + NB * ((m + NB - 1) / NB);
-            if ((rc = upload_test_inputs(ctx, D, m, 0, m, Xs + r0, ldxs))) return rc;
-            if ((rc = lap_on_ws(ctx, [&] {
-                     lap_query_launches(s, d, N, m, lda, ctx->A, ctx->dX, dy, ctx->dXs, ctx->dtp, lap, ctx->dY);
-                 })))
-                return rc;
-            xr = ExtraRows::responses(m, ctx->dY, N);
-        } else {
-            // (the gradient: B in the layout of its identity rows, which leave Y = L^{-T} below it)
-            if (grad) xr = ExtraRows::identity(N, singletons).deferred();
-            if ((rc = lap_on_ws(ctx, [&] {
-                     lap_build_launches(s, d, N, grad ? 2 * d.Np : d.Np, false, ctx->A, ctx->dX, dy, ctx->dtp, lap);
-                 })))
-                return rc;
-        }
-        if ((rc = eval_device(ctx, N, D, tp, xr.on_prebuilt(), &r))) return rc;
-        if ((rc = finish(r, nullptr, nullptr, nullptr))) return fail_b(rc);
-        if (r0 == 0) logq = psi - 0.5 * r.logdet;
-        if (m > 0) {
-            if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, m, ctx->dX, ctx->dXs, m, ctx->dtp, lap, d.a, d.mean); })))
-                return rc;
-            quad.resize((size_t)m);
-            HIPCK(ctx, hipMemcpyAsync(quad.data(), ctx->mres, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-            if (out_mean) HIPCK(ctx, hipMemcpyAsync(out_mean + r0, lap + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-            HIPCK(ctx, hipStreamSynchronize(s));
-            for (int64_t j = 0; out_var && j < m; ++j)
-                out_var[r0 + j] = host_kdiag(tp, Xs, ldxs, r0 + j) - quad[(size_t)j];
-        }
+    return h[3] > 0.0 ? lap_bad_w(ctx, q.N, h[3], out_info) : 0;
+}
+
+// One Newton step from (a, f) with its halving line search. *moved: a step was accepted and is
+// the new iterate; *converged: and psi changed by no more than tol (relative).
+static int lap_newton_step(gaplac_ctx* ctx, const LapRequest& q, const LapDims& d, const TermPack& tp,
+                           int64_t* out_info, bool* moved, bool* converged) {
+    int rc;
+    const int64_t N = q.N;
+    hipStream_t s = ctx->s_main;
+    double* const lap = ctx->lap;
+    const double* const dy = ctx->dv;
+    double h[4];
+    EvalResult r;
+    *moved = *converged = false;
+    // the likelihood at (a, f); c = K b; K and B; the factorisation
+    if ((rc = lap_lik_at_iterate(ctx, q, d, out_info, h))) return rc;
+    const double psi_old = h[2];
+    if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.b, d.c); })))
+        return rc;
+    if ((rc = lap_on_ws(ctx, [&] { lap_build_launches(s, d, N, d.Np, true, ctx->A, ctx->dX, dy, ctx->dtp, lap); })))
+        return rc;
+    if ((rc = eval_device(ctx, N, q.D, tp, ExtraRows{}.on_prebuilt(), &r))) return rc;
+    if ((rc = finish(r, nullptr, nullptr, nullptr))) return lap_bad_b(ctx, N, rc, out_info);
+    // u = B^{-1} (sw c), a+ = b - sw u, f+ = K a+
+    if ((rc = lap_on_ws(ctx, [&] { lap_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
+    if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.an, d.fn); })))
+        return rc;
+    if ((rc = lap_on_ws(ctx, [&] { lap_fnew_launches(s, d, N, lap); }))) return rc;
+    // the step: the first s = 1, 1/2, ... whose psi is finite and no worse than psi_old (to rounding)
+    double step = 1.0, psi_new = NAN;
+    for (int hv = 0; hv <= 20 && !*moved; ++hv, step *= 0.5) {
+        if ((rc = lap_on_ws(ctx, [&] { lap_trial_launches(s, d, N, q.lik, q.lik_param, step, dy, lap); }))) return rc;
+        if ((rc = lap_read_sums(ctx, d, h))) return rc;
+        psi_new = h[2];
+        *moved = std::isfinite(psi_new) && psi_new >= psi_old - q.tol * (1.0 + std::fabs(psi_old));
     }
-    double himp[GAPLAC_MAX_TERMS + 1];
-    if (grad) {
-        // Y's rows times sw (Y Y^T = R) and diag B^{-1}; s2, q = K s2, u = s2 - R q; the explicit part
-        // by the gradient's ending with alpha = a; the implicit part matrix-free
-        EvalScope scope(ctx, ExtraRows::identity(N, singletons));
-        if ((rc = lap_on_ws(ctx, [&] { lap_grad_scale_launches(s, d, N, lik, ctx->A, lap); }))) return rc;
-        if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.s2, d.q); })))
-            return rc;
-        if ((rc = lap_on_ws(ctx, [&] { lap_grad_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
-        int erc = 0;
-        if ((rc = lap_on_ws(ctx, [&] { erc = enqueue_grad_ending(ctx, N, d.Np, 2 * d.Np, lap + d.a); }))) return rc;
-        if (erc) return erc;
-        if ((rc = lap_on_ws(ctx, [&] { lap_grad_bilinear_launches(s, d, N, T, ctx->dX, ctx->dtp, ctx->dgp, lap); })))
-            return rc;
-        HIPCK(ctx, hipMemcpyAsync(himp, lap + d.gimp, (size_t)(T + 1) * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (out_f) HIPCK(ctx, hipMemcpyAsync(out_f, lap + d.f, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    if (out_a) HIPCK(ctx, hipMemcpyAsync(out_a, lap + d.a, (size_t)N * 8, hipMemcpyDeviceToHost, s));
-    HIPCK(ctx, hipStreamSynchronize(s));
-    if (fit) {  // (M = 0, no gradient: the workspace holds B's factor with ld Np)
-        std::unique_ptr<gaplac_fit> f = lap_fit_new(ctx, N, D, T, terms, tp, fit->cap, lik, lik_param, jitter);
-        f->logpdf = logq;
-        f->logdet = r.logdet;
-        f->quad = atf;
-        f->iters = iters;
-        f->converged = converged ? 1 : 0;
-        if ((rc = lap_fit_fill(ctx, f.get(), d))) return rc;
-        f->ctx = ctx;
-        ctx->fits.push_back(f.get());
-        *fit->out = f.release();
-    }
-    if (grad) {  // explicit (ctx->hgout, copied by the ending) + implicit
-        for (int t = 0; t < T; ++t)
-            if (grad->dparam) grad->dparam[t] = ctx->hgout[t] + himp[t];
-        if (grad->djitter) *grad->djitter = ctx->hgout[T] + himp[T];
-        for (int t = 0; t <= T; ++t)
-            if (grad->implicit) grad->implicit[t] = himp[t];
-    }
-    *out_logq = logq;
-    if (out_iters) *out_iters = iters;
-    if (out_converged) *out_converged = converged ? 1 : 0;
+    if (!*moved) return 0;  // no acceptable step: the iterate stays
+    HIPCK(ctx, hipMemcpyAsync(lap + d.a, lap + d.at, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    HIPCK(ctx, hipMemcpyAsync(lap + d.f, lap + d.ft, (size_t)N * 8, hipMemcpyDeviceToDevice, s));
+    *converged = std::fabs(psi_new - psi_old) <= q.tol * (1.0 + std::fabs(psi_new));
     return 0;
 }
+
+// The final factorisation of B with one chunk of test points riding (rows [r0, r0 + m) of Xs, their mean
+// and variance out), or with M = 0 plain (the gradient: with its identity rows, which leave Y = L^{-T}).
+static int lap_final_chunk(gaplac_ctx* ctx, const LapRequest& q, const LapOut& o, const LapDims& d,
+                           const TermPack& tp, int64_t r0, bool singletons, EvalResult* r) {
+    int rc;
+    const int64_t N = q.N, m = std::min(LAP_CHUNK, q.M - r0);
+    hipStream_t s = ctx->s_main;
+    double* const lap = ctx->lap;
+    ExtraRows xr;
+    if (m > 0) {
+        const int64_t lda = d.Np + NB * ((m + NB - 1) / NB);
+        if ((rc = upload_test_inputs(ctx, q.D, m, 0, m, q.Xs + r0, q.ldxs))) return rc;
+        if ((rc = lap_on_ws(ctx, [&] {
+                 lap_query_launches(s, d, N, m, lda, ctx->A, ctx->dX, ctx->dv, ctx->dXs, ctx->dtp, lap, ctx->dY);
+             })))
+            return rc;
+        xr = ExtraRows::responses(m, ctx->dY, N);
+    } else {
+        if (o.grad) xr = ExtraRows::identity(N, singletons).deferred();
+        if ((rc = lap_on_ws(ctx, [&] {
+                 lap_build_launches(s, d, N, o.grad ? 2 * d.Np : d.Np, false, ctx->A, ctx->dX, ctx->dv, ctx->dtp, lap);
+             })))
+            return rc;
+    }
+    if ((rc = eval_device(ctx, N, q.D, tp, xr.on_prebuilt(), r))) return rc;
+    if ((rc = finish(*r, nullptr, nullptr, nullptr))) return lap_bad_b(ctx, N, rc, o.info);
+    if (m <= 0) return 0;
+    if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, m, ctx->dX, ctx->dXs, m, ctx->dtp, lap, d.a, d.mean); })))
+        return rc;
+    std::vector<double> quad((size_t)m);
+    HIPCK(ctx, hipMemcpyAsync(quad.data(), ctx->mres, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    if (o.mean) HIPCK(ctx, hipMemcpyAsync(o.mean + r0, lap + d.mean, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(ctx, hipStreamSynchronize(s));
+    for (int64_t j = 0; o.var && j < m; ++j) o.var[r0 + j] = host_kdiag(tp, q.Xs, q.ldxs, r0 + j) - quad[(size_t)j];
+    return 0;
+}
+
+// The gradient's stages after the final factorisation with identity rows: Y's rows times sw (Y Y^T = R)
+// and diag B^{-1}; s2, q = K s2, u = s2 - R q; the explicit part by the gradient's ending with alpha = a
+// (into ctx->hgout); the implicit part matrix-free, into himp (T + 1 values, once s_main has retired).
+static int lap_grad_stages(gaplac_ctx* ctx, const LapRequest& q, const LapDims& d, bool singletons, double* himp) {
+    int rc, erc = 0;
+    const int64_t N = q.N;
+    hipStream_t s = ctx->s_main;
+    double* const lap = ctx->lap;
+    EvalScope scope(ctx, ExtraRows::identity(N, singletons));
+    if ((rc = lap_on_ws(ctx, [&] { lap_grad_scale_launches(s, d, N, q.lik, ctx->A, lap); }))) return rc;
+    if ((rc = lap_on_vectors(ctx, [&] { lap_mf_launches(s, d, N, N, ctx->dX, ctx->dX, N, ctx->dtp, lap, d.s2, d.q); })))
+        return rc;
+    if ((rc = lap_on_ws(ctx, [&] { lap_grad_solve_launches(s, d, N, ctx->A, lap); }))) return rc;
+    if ((rc = lap_on_ws(ctx, [&] { erc = enqueue_grad_ending(ctx, N, d.Np, 2 * d.Np, lap + d.a); }))) return rc;
+    if (erc) return erc;
+    if ((rc = lap_on_ws(ctx, [&] { lap_grad_bilinear_launches(s, d, N, q.T, ctx->dX, ctx->dtp, ctx->dgp, lap); })))
+        return rc;
+    HIPCK(ctx, hipMemcpyAsync(himp, lap + d.gimp, (size_t)(q.T + 1) * 8, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// Shared body of gaplac_laplace_logpdf, gaplac_laplace_posterior_mean_var (q.M test points),
+// gaplac_laplace_logpdf_grad (o.grad) and gaplac_laplace_fit_create (o.fit), phase by phase.
+static int laplace_impl(gaplac_ctx* ctx, const LapRequest& q, const LapOut& o) {
+    lap_fill_out(q, o, NAN);
+    TermPack tp;
+    int rc = lap_check(ctx, q, o, &tp);
+    if (rc) return rc;
+    if (q.N == 0) {  // no observations: log q = 0, a zero gradient, the prior at the test points, the empty fit
+        lap_fill_out(q, o, 0.0);
+        if (o.converged) *o.converged = 1;
+        for (int64_t j = 0; o.var && j < q.M; ++j) o.var[j] = host_kdiag(tp, q.Xs, q.ldxs, j);
+        return o.fit ? lap_fit_hand_out(ctx, q, o, tp, nullptr, LapResult{0.0, 0.0, 0.0, 0, true}) : 0;
+    }
+    tp.noise = q.jitter;
+    const int64_t N = q.N;
+    const LapDims d = lap_dims(N, q.M, o.grad);
+    if ((d.qc + NB - 1) / NB > 65535 || (N + NB - 1) / NB > 65535 || (o.fit && (o.cap + NB - 1) / NB > 65535))
+        return set_err(ctx, GAPLAC_E_OOM, "more than 65535 tile rows in one call");
+    bool singletons = true;
+    if ((rc = lap_upload(ctx, q, d, tp, o.grad, &singletons))) return rc;
+    LapResult res{NAN, NAN, NAN, 0, false};
+    for (int it = 0; it < q.max_iter && !res.converged; ++it) {
+        bool moved;
+        if ((rc = lap_newton_step(ctx, q, d, tp, o.info, &moved, &res.converged))) return rc;
+        if (!moved) break;  // not converged
+        ++res.iters;
+    }
+    // W at the last iterate, B factored once more (with the first chunk of test points riding)
+    double h[4];
+    if ((rc = lap_lik_at_iterate(ctx, q, d, o.info, h))) return rc;
+    res.atf = h[1];
+    for (int64_t r0 = 0; r0 == 0 || r0 < q.M; r0 += LAP_CHUNK) {
+        EvalResult r;
+        if ((rc = lap_final_chunk(ctx, q, o, d, tp, r0, singletons, &r))) return rc;
+        if (r0 == 0) res.logq = h[2] - 0.5 * r.logdet;
+        res.logdet = r.logdet;
+    }
+    double himp[GAPLAC_MAX_TERMS + 1];
+    if (o.grad && (rc = lap_grad_stages(ctx, q, d, singletons, himp))) return rc;
+    hipStream_t s = ctx->s_main;
+    if (o.f) HIPCK(ctx, hipMemcpyAsync(o.f, ctx->lap + d.f, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    if (o.a) HIPCK(ctx, hipMemcpyAsync(o.a, ctx->lap + d.a, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+    HIPCK(ctx, hipStreamSynchronize(s));
+    // (the fit: M = 0, no gradient: the workspace holds B's factor with ld Np)
+    if (o.fit && (rc = lap_fit_hand_out(ctx, q, o, tp, &d, res))) return rc;
+    if (o.grad) {  // explicit (ctx->hgout, copied by the ending) + implicit
+        for (int t = 0; o.dparam && t < q.T; ++t) o.dparam[t] = ctx->hgout[t] + himp[t];
+        if (o.djitter) *o.djitter = ctx->hgout[q.T] + himp[q.T];
+        for (int t = 0; o.implicit && t <= q.T; ++t) o.implicit[t] = himp[t];
+    }
+    *o.logq = res.logq;
+    if (o.iters) *o.iters = res.iters;
+    if (o.converged) *o.converged = res.converged ? 1 : 0;
+    return 0;
+}
+
+// ---- parts that several plan checks share ----
+// The Laplace entries' two guards over fake regions: the twins of lap_on_ws and lap_on_vectors.
+struct LapWalk {
+    PlanWalk& w;
+    int64_t a_elems, l_elems, y_elems;
+    double *const fa = PlanWalk::region(0), *const fl = PlanWalk::region(1), *const fy = PlanWalk::region(2);
+    template <typename L> void on_ws(L&& run) { w.on(fa, a_elems, fl, l_elems, run, y_elems ? fy : nullptr, y_elems); }
+    template <typename L> void on_vectors(L&& run) { w.on(fl, l_elems, nullptr, 0, run); }
+};
+
+// lap_newton_step with one trial point, then the likelihood at the new iterate: both Laplace walks' start.
+static void walk_lap_iteration(LapWalk& lw, const LapDims& d, int64_t N) {
+    double *const fa = lw.fa, *const fl = lw.fl;
+    const int lik = GAPLAC_LIK_POISSON;
+    lw.on_ws([&] { lap_lik_launches(nullptr, d, N, lik, 0.0, nullptr, fl); });
+    lw.on_vectors([&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.b, d.c); });
+    lw.on_ws([&] { lap_build_launches(nullptr, d, N, d.Np, true, fa, nullptr, nullptr, nullptr, fl); });
+    lw.w.eval(N, ExtraRows{}.on_prebuilt());
+    lw.on_ws([&] { lap_solve_launches(nullptr, d, N, fa, fl); });
+    lw.on_vectors([&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.an, d.fn); });
+    lw.on_ws([&] { lap_fnew_launches(nullptr, d, N, fl); });
+    lw.on_ws([&] { lap_trial_launches(nullptr, d, N, lik, 0.0, 1.0, nullptr, fl); });
+    lw.on_ws([&] { lap_lik_launches(nullptr, d, N, lik, 0.0, nullptr, fl); });
+}
+
+// The sparse entries' three stages (see gaplac_plan_check_sparse), also the first part of the sparse
+// gradient's and the sparse joint walks. false, and nothing walked: the arguments are out of range.
+static bool walk_sparse(PlanWalk& w, int64_t N, int64_t Mz, int64_t Ms, int32_t short_ws) {
+    if (N < 1 || Mz < 1 || Ms < 0 || w.spw < 1 || w.spw > 8 || short_ws < 0 || short_ws > 2) return false;
+    if ((N + Ms + NB - 1) / NB > 65535) return false;
+    const SparseDims d = sparse_dims(N, Mz, Ms);
+    double *const fa = PlanWalk::region(0), *const fb = PlanWalk::region(1);
+    const int64_t a_elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0), b_elems = d.ldb * d.Np - (short_ws == 2 ? 1 : 0);
+    w.eval(Mz, ExtraRows::test_points(N + Ms), short_ws == 1 ? 1 : 0);
+    w.on(fa, a_elems, fb, b_elems, [&] {
+        sparse_s_launches(nullptr, d, N, Mz, fa, nullptr, nullptr, fb, 1.0);
+        sparse_rows_launches(nullptr, d, N, Mz, Ms, fa, nullptr);
+    });
+    const ExtraRows rows = Ms > 0 ? ExtraRows::responses(Ms, nullptr, 0) : ExtraRows{};
+    w.eval(Mz, rows.on_prebuilt(), short_ws == 2 ? 1 : 0);
+    w.on(fb, b_elems, nullptr, 0, [&] { sparse_post_launches(nullptr, d, Mz, Ms, 1.0, fb, nullptr, nullptr, nullptr); });
+    return true;
+}
+}  // namespace
 
 extern "C" {
 
@@ -4007,23 +4055,24 @@ int gaplac_rand_multi(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, in
 int gaplac_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                               const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
                               int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
-    return posterior_mean_cov_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, out_mean, out_cov,
-                                   ldc);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y};
+    return joint_mean_cov(ctx, m, M, Xs, ldxs, noise_s, out_mean, out_cov, ldc);
 }
 
 int gaplac_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                           const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
                           int64_t ldxs, double noise_s, int64_t R, const double* Z, int64_t ldz, double* out,
                           int64_t ldo) {
-    return posterior_rand_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, R, Z, ldz, out, ldo);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y};
+    return joint_rand(ctx, m, M, Xs, ldxs, noise_s, R, Z, ldz, out, ldo);
 }
 
 int gaplac_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                             const gaplac_term* terms, double noise, const double* y, int64_t M, const double* Xs,
                             int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
                             double* out_logpdf, double* out_logdet, double* out_quad) {
-    return posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, M, Xs, ldxs, noise_s, R, Ys, ldys, out_logpdf,
-                                 out_logdet, out_quad);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y};
+    return joint_logpdf(ctx, m, M, Xs, ldxs, noise_s, R, Ys, ldys, out_logpdf, out_logdet, out_quad);
 }
 
 int gaplac_sparse_elbo(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
@@ -4062,16 +4111,16 @@ int gaplac_sparse_posterior_mean_cov(gaplac_ctx* ctx, int64_t N, int32_t D, cons
                                      const gaplac_term* terms, double noise, const double* y, int64_t Mz,
                                      const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
                                      int64_t ldxs, double noise_s, double* out_mean, double* out_cov, int64_t ldc) {
-    return sparse_posterior_mean_cov_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs,
-                                          noise_s, out_mean, out_cov, ldc);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y, true, Mz, Z, ldz, jitter};
+    return joint_mean_cov(ctx, m, Ms, Xs, ldxs, noise_s, out_mean, out_cov, ldc);
 }
 
 int gaplac_sparse_posterior_rand(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                                  const gaplac_term* terms, double noise, const double* y, int64_t Mz, const double* Z,
                                  int64_t ldz, double jitter, int64_t Ms, const double* Xs, int64_t ldxs,
                                  double noise_s, int64_t R, const double* E, int64_t lde, double* out, int64_t ldo) {
-    return sparse_posterior_rand_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs, noise_s,
-                                      R, E, lde, out, ldo);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y, true, Mz, Z, ldz, jitter};
+    return joint_rand(ctx, m, Ms, Xs, ldxs, noise_s, R, E, lde, out, ldo);
 }
 
 int gaplac_sparse_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
@@ -4079,13 +4128,8 @@ int gaplac_sparse_posterior_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const 
                                    const double* Z, int64_t ldz, double jitter, int64_t Ms, const double* Xs,
                                    int64_t ldxs, double noise_s, int64_t R, const double* Ys, int64_t ldys,
                                    double* out_logpdf, double* out_logdet, double* out_quad) {
-    return sparse_posterior_logpdf_impl(ctx, N, D, X, ldx, T, terms, noise, y, Mz, Z, ldz, jitter, Ms, Xs, ldxs,
-                                        noise_s, R, Ys, ldys, out_logpdf, out_logdet, out_quad);
-}
-
-int gaplac_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
-                      const gaplac_term* terms, double noise, const double* y, int64_t cap, gaplac_fit** out) {
-    return fit_create_impl(ctx, N, D, X, ldx, T, terms, noise, y, cap, out);
+    const JointModel m{N, D, X, ldx, T, terms, noise, y, true, Mz, Z, ldz, jitter};
+    return joint_logpdf(ctx, m, Ms, Xs, ldxs, noise_s, R, Ys, ldys, out_logpdf, out_logdet, out_quad);
 }
 
 int gaplac_fit_destroy(gaplac_fit* fit) {
@@ -4122,20 +4166,6 @@ int gaplac_fit_alpha(gaplac_fit* fit, double* out_alpha) {
     return 0;
 }
 
-int gaplac_fit_mean(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean) {
-    return fit_mean_impl(fit, M, Xs, ldxs, out_mean);
-}
-
-int gaplac_fit_mean_var(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double* out_mean,
-                        double* out_var) {
-    return fit_mean_var_impl(fit, M, Xs, ldxs, out_mean, out_var);
-}
-
-int gaplac_fit_mean_cov(gaplac_fit* fit, int64_t M, const double* Xs, int64_t ldxs, double noise_s, double* out_mean,
-                        double* out_cov, int64_t ldc) {
-    return fit_mean_cov_impl(fit, M, Xs, ldxs, noise_s, out_mean, out_cov, ldc);
-}
-
 int gaplac_fit_mode(gaplac_fit* fit, double* out_f) {
     if (!fit) return GAPLAC_E_ARG;
     for (int64_t i = 0; out_f && i < fit->N; ++i) out_f[i] = NAN;
@@ -4166,10 +4196,12 @@ int gaplac_laplace_fit_create(gaplac_ctx* ctx, int64_t N, int32_t D, const doubl
     if (out) *out = nullptr;
     if (!ctx) return GAPLAC_E_ARG;
     if (!out) return set_err(ctx, GAPLAC_E_ARG, "out is NULL");
-    const LapFitOut fo{cap, out};
+    const LapRequest q{N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0};
     double logq;
-    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0, nullptr, 0,
-                        &logq, nullptr, nullptr, nullptr, nullptr, out_iters, out_converged, out_info, nullptr, &fo);
+    LapOut o{&logq, out_iters, out_converged, out_info};
+    o.fit = out;
+    o.cap = cap;
+    return laplace_impl(ctx, q, o);
 }
 
 // Host-only walk of a Laplace fit (no device needed; the iteration and its final factorisation are
@@ -4185,26 +4217,14 @@ int gaplac_plan_check_laplace_fit(int64_t N, int64_t cap, int64_t M, int32_t spw
     const FitDims d = fit_dims(N, 1, cap, true);
     const LapDims ld = lap_dims(N, 0);
     const int64_t mc = std::min(M, cap), ldb = round_up(mc + 1, NB);
-    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 46);
-    double* const fB = reinterpret_cast<double*>((uintptr_t)1 << 47);
-    LaunchGuard gc, gq;  // the create: buffer, workspace, vectors; the queries: buffer, second workspace
-    gc.base = gq.base = fb;
-    gc.elems = gq.elems = d.elems - (short_ws == 1 ? 1 : 0);
-    gc.base2 = fa;
-    gc.elems2 = ld.a_elems;
-    gc.base3 = fl;
-    gc.elems3 = ld.elems;
-    gq.base2 = fB;
-    gq.elems2 = ldb * ldb - (short_ws == 2 ? 1 : 0);
-    gc.dry = gq.dry = true;
-    {
-        GuardScope scope(&gc);
-        lap_fit_create_launches(nullptr, d, ld, N, fa, fl, fb);
-    }
-    {
-        GuardScope scope(&gq);
+    double* const fb = PlanWalk::region(0);  // the fit's buffer
+    double* const fa = PlanWalk::region(1);  // the workspace
+    double* const fl = PlanWalk::region(2);  // the vectors
+    double* const fB = PlanWalk::region(3);  // the second workspace
+    const int64_t b_elems = d.elems - (short_ws == 1 ? 1 : 0), B_elems = ldb * ldb - (short_ws == 2 ? 1 : 0);
+    PlanWalk w{spw};
+    w.on(fb, b_elems, fa, ld.a_elems, [&] { lap_fit_create_launches(nullptr, d, ld, N, fa, fl, fb); }, fl, ld.elems);
+    w.on(fb, b_elems, fB, B_elems, [&] {
         for (int64_t r0 = 0; r0 < M; r0 += cap)
             fit_query_launches(nullptr, d, N, std::min(cap, M - r0), spw, fb, true);
         for (int64_t r0 = 0; r0 < M; r0 += d.qc) fit_mean_launches(nullptr, d, N, std::min(d.qc, M - r0), fb);
@@ -4212,11 +4232,8 @@ int gaplac_plan_check_laplace_fit(int64_t N, int64_t cap, int64_t M, int32_t spw
             fit_query_launches(nullptr, d, N, mc, spw, fb, true);
             fit_cov_launches(nullptr, d, N, mc, fb, fB, ldb, nullptr);
         }
-    }
-    if (out_launches) *out_launches = gc.launches + gq.launches;
-    if (out_violations) *out_violations = gc.violations + gq.violations;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", (gc.violations ? gc.first : gq.first).c_str());
-    return 0;
+    });
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of a fit (no device needed): the create-time copy, z and the back-substitution
@@ -4228,32 +4245,25 @@ int gaplac_plan_check_fit(int64_t N, int64_t cap, int64_t M, int32_t spw, int32_
     if (N < 1 || cap < 1 || M < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 1) return GAPLAC_E_ARG;
     if ((cap + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
     const FitDims d = fit_dims(N, 1, cap);
-    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    LaunchGuard g;
-    g.base = fb;
-    g.elems = d.elems - (short_ws == 1 ? 1 : 0);
-    g.base2 = fa;
-    g.elems2 = d.Np * d.Np;
-    g.dry = true;
-    {
-        GuardScope scope(&g);
+    double *const fb = PlanWalk::region(0), *const fa = PlanWalk::region(1);
+    PlanWalk w{spw};
+    w.on(fb, d.elems - (short_ws == 1 ? 1 : 0), fa, d.Np * d.Np, [&] {
         fit_create_launches(nullptr, d, N, fa, d.Np, fb);
         for (int64_t r0 = 0; r0 < M; r0 += cap) fit_query_launches(nullptr, d, N, std::min(cap, M - r0), spw, fb);
         for (int64_t r0 = 0; r0 < M; r0 += d.qc) fit_mean_launches(nullptr, d, N, std::min(d.qc, M - r0), fb);
-    }
-    if (out_launches) *out_launches = g.launches;
-    if (out_violations) *out_violations = g.violations;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
-    return 0;
+    });
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 int gaplac_laplace_logpdf(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
                           const gaplac_term* terms, double jitter, int32_t lik, double lik_param, const double* y,
                           int32_t max_iter, double tol, const double* a0, double* out_logq, double* out_f,
                           double* out_a, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
-    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0, nullptr, 0,
-                        out_logq, out_f, out_a, nullptr, nullptr, out_iters, out_converged, out_info);
+    const LapRequest q{N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0};
+    LapOut o{out_logq, out_iters, out_converged, out_info};
+    o.f = out_f;
+    o.a = out_a;
+    return laplace_impl(ctx, q, o);
 }
 
 int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
@@ -4261,8 +4271,11 @@ int gaplac_laplace_posterior_mean_var(gaplac_ctx* ctx, int64_t N, int32_t D, con
                                       const double* y, int32_t max_iter, double tol, const double* a0, int64_t M,
                                       const double* Xs, int64_t ldxs, double* out_logq, double* out_mean,
                                       double* out_var, int32_t* out_iters, int32_t* out_converged, int64_t* out_info) {
-    return laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, true, M, Xs, ldxs,
-                        out_logq, nullptr, nullptr, out_mean, out_var, out_iters, out_converged, out_info);
+    const LapRequest q{N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, M, Xs, ldxs};
+    LapOut o{out_logq, out_iters, out_converged, out_info};
+    o.mean = out_mean;
+    o.var = out_var;
+    return laplace_impl(ctx, q, o);
 }
 
 int gaplac_laplace_logpdf_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const double* X, int64_t ldx, int32_t T,
@@ -4270,11 +4283,16 @@ int gaplac_laplace_logpdf_grad(gaplac_ctx* ctx, int64_t N, int32_t D, const doub
                                const double* y, int32_t max_iter, double tol, const double* a0, double* out_logq,
                                double* out_f, double* out_a, int32_t* out_iters, int32_t* out_converged,
                                int64_t* out_info, double* out_dparam, double* out_djitter, double* out_implicit) {
-    const LapGradOut g{out_dparam, out_djitter, out_implicit};
+    const LapRequest q{N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0};
     double logq;
-    const int rc = laplace_impl(ctx, N, D, X, ldx, T, terms, jitter, lik, lik_param, y, max_iter, tol, a0, false, 0,
-                                nullptr, 0, &logq, out_f, out_a, nullptr, nullptr, out_iters, out_converged, out_info,
-                                &g);
+    LapOut o{&logq, out_iters, out_converged, out_info};  // (out_logq may be NULL here)
+    o.f = out_f;
+    o.a = out_a;
+    o.grad = true;
+    o.dparam = out_dparam;
+    o.djitter = out_djitter;
+    o.implicit = out_implicit;
+    const int rc = laplace_impl(ctx, q, o);
     if (out_logq) *out_logq = logq;
     return rc;
 }
@@ -4286,66 +4304,25 @@ int gaplac_plan_check_laplace_grad(int64_t N, int32_t spw, int32_t short_ws, int
                                    int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
     const LapDims d = lap_dims(N, 0, true);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    LaunchGuard gw, gv;  // the workspace (with the vectors); the vectors alone
-    gw.base = fa;
-    gw.elems = d.a_elems - (short_ws == 1 ? 1 : 0);
-    gw.base2 = gv.base = fl;
-    gw.elems2 = gv.elems = d.elems - (short_ws == 2 ? 1 : 0);
-    gw.dry = gv.dry = true;
-    std::vector<LaunchGuard> evals;
-    int rc = 0;
-    auto on = [](LaunchGuard& g, auto&& launches) {
-        GuardScope scope(&g);
-        launches();
-    };
-    auto eval = [&](const ExtraRows& xr, const std::function<int(gaplac_ctx&)>& after) {
-        gaplac_ctx c;
-        c.spw = spw;
-        evals.emplace_back();
-        LaunchGuard& g = evals.back();
-        g.base2 = fl;
-        g.elems2 = gw.elems2;
-        int e = dry_walk(c, N, xr.on_prebuilt(), g, 0, after);
-        if (e == GAPLAC_E_ARG && g.violations) e = 0;
-        if (rc == 0) rc = e;
-    };
-    on(gw, [&] { lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl); });
-    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.b, d.c); });
-    on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, true, fa, nullptr, nullptr, nullptr, fl); });
-    eval(ExtraRows{}, nullptr);
-    on(gw, [&] { lap_solve_launches(nullptr, d, N, fa, fl); });
-    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.an, d.fn); });
-    on(gw, [&] {
-        lap_fnew_launches(nullptr, d, N, fl);
-        lap_trial_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, 1.0, nullptr, fl);
-        lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl);
-        lap_build_launches(nullptr, d, N, 2 * d.Np, false, fa, nullptr, nullptr, nullptr, fl);
-    });
+    PlanWalk w{spw};
+    LapWalk lw{w, d.a_elems - (short_ws == 1 ? 1 : 0), d.elems - (short_ws == 2 ? 1 : 0), 0};
+    double *const fa = lw.fa, *const fl = lw.fl;
+    walk_lap_iteration(lw, d, N);
+    lw.on_ws([&] { lap_build_launches(nullptr, d, N, 2 * d.Np, false, fa, nullptr, nullptr, nullptr, fl); });
     // the final factorisation; then, in its (dry) context, the gradient's stages: the stages under
     // the entry's guards, the ending under the walk's own (the workspace of 2 Np x Np elements)
-    // (twice: single-term groups, the fused contraction; product groups, its two-launch form)
+    // (twice: single-term groups, the fused contraction; product groups, its two-launch form). The vectors
+    // are the evaluation's second region for the ending; the step's evaluation, with no `after`, needs none.
     for (bool singletons : {true, false})
-        eval(ExtraRows::identity(N, singletons).deferred(), [&](gaplac_ctx& c) {
-            on(gw, [&] { lap_grad_scale_launches(nullptr, d, N, GAPLAC_LIK_POISSON, fa, fl); });
-            on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.s2, d.q); });
-            on(gw, [&] { lap_grad_solve_launches(nullptr, d, N, fa, fl); });
+        w.eval(N, ExtraRows::identity(N, singletons).deferred().on_prebuilt(), 0, [&](gaplac_ctx& c) {
+            lw.on_ws([&] { lap_grad_scale_launches(nullptr, d, N, GAPLAC_LIK_POISSON, fa, fl); });
+            lw.on_vectors([&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.s2, d.q); });
+            lw.on_ws([&] { lap_grad_solve_launches(nullptr, d, N, fa, fl); });
             const int e = enqueue_grad_ending(&c, N, d.Np, 2 * d.Np, fl + d.a);
-            on(gw, [&] { lap_grad_bilinear_launches(nullptr, d, N, 1, nullptr, nullptr, nullptr, fl); });
+            lw.on_ws([&] { lap_grad_bilinear_launches(nullptr, d, N, 1, nullptr, nullptr, nullptr, fl); });
             return e;
-        });
-    int64_t launches = gw.launches + gv.launches, violations = gw.violations + gv.violations;
-    std::string first = gw.violations ? gw.first : gv.first;
-    for (const LaunchGuard& g : evals) {
-        launches += g.launches;
-        if (violations == 0 && g.violations) first = g.first;
-        violations += g.violations;
-    }
-    if (out_launches) *out_launches = launches;
-    if (out_violations) *out_violations = violations;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
-    return rc;
+        }, fl, lw.l_elems);
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of the Laplace entries (no device needed): one Newton step with one trial point,
@@ -4356,65 +4333,23 @@ int gaplac_plan_check_laplace(int64_t N, int64_t M, int32_t spw, int32_t short_w
                               int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || M < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 1) return GAPLAC_E_ARG;
     const LapDims d = lap_dims(N, M);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fl = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    double* const fy = reinterpret_cast<double*>((uintptr_t)1 << 46);
-    LaunchGuard gw, gv;  // the workspace (with the vectors and the responses); the vectors alone
-    gw.base = fa;
-    gw.elems = d.a_elems - short_ws;
-    gw.base2 = gv.base = fl;
-    gw.elems2 = gv.elems = d.elems - short_ws;
-    gw.base3 = fy;
-    gw.elems3 = N * d.qc;
-    gw.dry = gv.dry = true;
-    std::vector<LaunchGuard> evals;
-    int rc = 0;
-    auto on = [](LaunchGuard& g, auto&& launches) {
-        GuardScope scope(&g);
-        launches();
-    };
-    auto eval = [&](const ExtraRows& xr) {
-        gaplac_ctx c;
-        c.spw = spw;
-        evals.emplace_back();
-        int e = dry_walk(c, N, xr.on_prebuilt(), evals.back());
-        if (e == GAPLAC_E_ARG && evals.back().violations) e = 0;
-        if (rc == 0) rc = e;
-    };
-    on(gw, [&] { lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl); });
-    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.b, d.c); });
-    on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, true, fa, nullptr, nullptr, nullptr, fl); });
-    eval(ExtraRows{});
-    on(gw, [&] { lap_solve_launches(nullptr, d, N, fa, fl); });
-    on(gv, [&] { lap_mf_launches(nullptr, d, N, N, nullptr, nullptr, N, nullptr, fl, d.an, d.fn); });
-    on(gw, [&] {
-        lap_fnew_launches(nullptr, d, N, fl);
-        lap_trial_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, 1.0, nullptr, fl);
-        lap_lik_launches(nullptr, d, N, GAPLAC_LIK_POISSON, 0.0, nullptr, fl);
-    });
+    PlanWalk w{spw};
+    LapWalk lw{w, d.a_elems - short_ws, d.elems - short_ws, N * d.qc};
+    double *const fa = lw.fa, *const fl = lw.fl;
+    walk_lap_iteration(lw, d, N);
     for (int64_t r0 = 0; r0 == 0 || r0 < M; r0 += LAP_CHUNK) {
         const int64_t m = std::min(LAP_CHUNK, M - r0);
         if (m > 0) {
             const int64_t lda = d.Np + NB * ((m + NB - 1) / NB);
-            on(gw, [&] { lap_query_launches(nullptr, d, N, m, lda, fa, nullptr, nullptr, nullptr, nullptr, fl, fy); });
-            eval(ExtraRows::responses(m, nullptr, 0));
-            on(gv, [&] { lap_mf_launches(nullptr, d, N, m, nullptr, nullptr, m, nullptr, fl, d.a, d.mean); });
+            lw.on_ws([&] { lap_query_launches(nullptr, d, N, m, lda, fa, nullptr, nullptr, nullptr, nullptr, fl, lw.fy); });
+            w.eval(N, ExtraRows::responses(m, nullptr, 0).on_prebuilt());
+            lw.on_vectors([&] { lap_mf_launches(nullptr, d, N, m, nullptr, nullptr, m, nullptr, fl, d.a, d.mean); });
         } else {
-            on(gw, [&] { lap_build_launches(nullptr, d, N, d.Np, false, fa, nullptr, nullptr, nullptr, fl); });
-            eval(ExtraRows{});
+            lw.on_ws([&] { lap_build_launches(nullptr, d, N, d.Np, false, fa, nullptr, nullptr, nullptr, fl); });
+            w.eval(N, ExtraRows{}.on_prebuilt());
         }
     }
-    int64_t launches = gw.launches + gv.launches, violations = gw.violations + gv.violations;
-    std::string first = gw.violations ? gw.first : gv.first;
-    for (const LaunchGuard& g : evals) {
-        launches += g.launches;
-        if (violations == 0 && g.violations) first = g.first;
-        violations += g.violations;
-    }
-    if (out_launches) *out_launches = launches;
-    if (out_violations) *out_violations = violations;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
-    return rc;
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out_chunk_rows) {
@@ -4432,44 +4367,9 @@ int gaplac_sparse_split(int64_t N, int64_t Mz, int64_t* out_chunks, int64_t* out
 // 1 / 2: the stage-1 / stage-3 workspace one element short (negative controls).
 int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int32_t short_ws, int64_t* out_launches,
                              int64_t* out_violations, char* msg, int64_t msglen) {
-    if (N < 1 || Mz < 1 || Ms < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
-    if ((N + Ms + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
-    const SparseDims d = sparse_dims(N, Mz, Ms);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    const int64_t a_elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0), b_elems = d.ldb * d.Np - (short_ws == 2 ? 1 : 0);
-    LaunchGuard g1, g2, g3, g4;
-    gaplac_ctx c1, c3;
-    c1.spw = c3.spw = spw;
-    int rc = dry_walk(c1, Mz, ExtraRows::test_points(N + Ms), g1, short_ws == 1 ? 1 : 0);
-    if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
-    if (rc == 0) {
-        g2.base = fa;
-        g2.elems = a_elems;
-        g2.base2 = fb;
-        g2.elems2 = b_elems;
-        g2.dry = true;
-        GuardScope scope(&g2);
-        sparse_s_launches(nullptr, d, N, Mz, fa, nullptr, nullptr, fb, 1.0);
-        sparse_rows_launches(nullptr, d, N, Mz, Ms, fa, nullptr);
-    }
-    if (rc == 0) {
-        const ExtraRows rows = Ms > 0 ? ExtraRows::responses(Ms, nullptr, 0) : ExtraRows{};
-        rc = dry_walk(c3, Mz, rows.on_prebuilt(), g3, short_ws == 2 ? 1 : 0);
-        if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
-    }
-    if (rc == 0) {
-        g4.base = fb;
-        g4.elems = b_elems;
-        g4.dry = true;
-        GuardScope scope(&g4);
-        sparse_post_launches(nullptr, d, Mz, Ms, 1.0, fb, nullptr, nullptr, nullptr);
-    }
-    if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches + g4.launches;
-    if (out_violations) *out_violations = g1.violations + g2.violations + g3.violations + g4.violations;
-    const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.violations ? g3.first : g4.first;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
-    return rc;
+    PlanWalk w{spw};
+    if (!walk_sparse(w, N, Mz, Ms, short_ws)) return GAPLAC_E_ARG;
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of gaplac_sparse_elbo_grad: the three stages of the value (gaplac_plan_check_sparse
@@ -4483,43 +4383,25 @@ int gaplac_plan_check_sparse(int64_t N, int64_t Mz, int64_t Ms, int32_t spw, int
 // region, one element short with short_ws 3.
 static int plan_sparse_grad(int64_t N, int64_t Mz, int32_t Tz, int32_t spw, int32_t short_ws, int64_t* out_launches,
                             int64_t* out_violations, char* msg, int64_t msglen) {
-    int64_t l0 = 0, v0 = 0;
-    int rc = gaplac_plan_check_sparse(N, Mz, 0, spw, short_ws == 3 ? 0 : short_ws, &l0, &v0, msg, msglen);
-    if (rc) return rc;
+    PlanWalk w{spw};
+    if (!walk_sparse(w, N, Mz, 0, short_ws == 3 ? 0 : short_ws)) return GAPLAC_E_ARG;
     const SparseDims d = sparse_dims(N, Mz, 0);
     const SparseGradDims g = sparse_grad_dims(Mz);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fg = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    double* const fv = reinterpret_cast<double*>((uintptr_t)1 << 46);  // vectors, partials, Dinv: never guarded
-    LaunchGuard g1, g2;
-    g1.base = fg;
-    g1.elems = 3 * g.ld * g.Np - (short_ws == 2 ? 1 : 0);
-    g1.dry = true;
-    g2.base = fa;
-    g2.elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0);
-    g2.base2 = fg;
-    g2.elems2 = g1.elems;
-    g2.dry = true;
-    double* const fz = Tz > 0 ? reinterpret_cast<double*>((uintptr_t)1 << 47) : nullptr;
-    if (fz) {  // (one column of Z: the finishing step's store is the buffer's last element for any D)
-        g2.base3 = fz;
-        g2.elems3 = sparse_dz_dims(N, Mz, Tz, 1).elems - (short_ws == 3 ? 1 : 0);
-    }
-    {
-        GuardScope scope(&g1);
-        sparse_grad_mz_launches(nullptr, g, Mz, fg, fv, fv, fv, fv, 1.0, nullptr, nullptr, nullptr, 1);
-    }
-    {
-        GuardScope scope(&g2);
+    double* const fa = PlanWalk::region(0);
+    double* const fg = PlanWalk::region(1);
+    double* const fv = PlanWalk::region(2);  // vectors, partials, Dinv: never guarded
+    // (one column of Z: the finishing step's store is the buffer's last element for any D)
+    double* const fz = Tz > 0 ? PlanWalk::region(3) : nullptr;
+    const int64_t g_elems = 3 * g.ld * g.Np - (short_ws == 2 ? 1 : 0);
+    const int64_t z_elems = fz ? sparse_dz_dims(N, Mz, Tz, 1).elems - (short_ws == 3 ? 1 : 0) : 0;
+    w.on(fg, g_elems, nullptr, 0,
+         [&] { sparse_grad_mz_launches(nullptr, g, Mz, fg, fv, fv, fv, fv, 1.0, nullptr, nullptr, nullptr, 1); });
+    w.on(fa, d.lda * d.Np - (short_ws == 1 ? 1 : 0), fg, g_elems, [&] {
         sparse_grad_alpha_launches(nullptr, d, g, N, Mz, fa, fv, fv, 1.0, nullptr);
         sparse_grad_uf_launches(nullptr, d, g, N, Mz, fa, fg, fv, fv, nullptr, nullptr, nullptr, nullptr, false,
                                 fz ? Tz : 1, fz, 1);
-    }
-    if (out_launches) *out_launches = l0 + g1.launches + g2.launches;
-    if (out_violations) *out_violations = v0 + g1.violations + g2.violations;
-    if (msg && msglen > 0 && v0 == 0 && (g1.violations || g2.violations))
-        std::snprintf(msg, (size_t)msglen, "%s", (g1.violations ? g1.first : g2.first).c_str());
-    return 0;
+    }, fz, z_elems);
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 int gaplac_plan_check_sparse_grad(int64_t N, int64_t Mz, int32_t spw, int32_t short_ws, int64_t* out_launches,
@@ -4549,50 +4431,23 @@ int gaplac_plan_check_sparse_joint(int64_t N, int64_t Mz, int64_t Ms, int64_t R,
                                    int64_t* out_launches, int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || Mz < 1 || Ms < 1 || R < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 3) return GAPLAC_E_ARG;
     if ((N + Ms + NB - 1) / NB > 65535 || (R + NB - 1) / NB > 65535) return GAPLAC_E_ARG;
-    int64_t l0 = 0, v0 = 0;
-    int rc = gaplac_plan_check_sparse(N, Mz, Ms, spw, short_ws == 3 ? 0 : short_ws, &l0, &v0, msg, msglen);
-    if (rc) return rc;
+    PlanWalk w{spw};
+    if (!walk_sparse(w, N, Mz, Ms, short_ws == 3 ? 0 : short_ws)) return GAPLAC_E_ARG;
     const SparseDims d = sparse_dims(N, Mz, Ms);
     const SparseJointDims j = sparse_joint_dims(Ms, R);
-    double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-    double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
-    double* const fc = reinterpret_cast<double*>((uintptr_t)1 << 46);
-    double* const fr = reinterpret_cast<double*>((uintptr_t)1 << 47);
+    double* const fa = PlanWalk::region(0);
+    double* const fb = PlanWalk::region(1);
+    double* const fc = PlanWalk::region(2);
+    double* const fr = PlanWalk::region(3);
     const int64_t a_elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0), b_elems = d.ldb * d.Np - (short_ws == 2 ? 1 : 0);
     const int64_t c_elems = j.ldc * j.Msp - (short_ws == 3 ? 1 : 0), r_elems = d.Np * j.ldr;
-    LaunchGuard g1, g2, g3;
-    g1.base = fa;
-    g1.elems = a_elems;
-    g1.base2 = fr;
-    g1.elems2 = r_elems;
-    g1.dry = true;
-    {
-        GuardScope scope(&g1);
-        sparse_joint_copy_launches(nullptr, d, j, N, Mz, Ms, fa, fr);
-    }
-    g2.base = fb;
-    g2.elems = b_elems;
-    g2.base2 = fc;
-    g2.elems2 = c_elems;
-    g2.base3 = fr;
-    g2.elems3 = r_elems;
-    g2.dry = true;
-    {
-        GuardScope scope(&g2);
+    w.on(fa, a_elems, fr, r_elems, [&] { sparse_joint_copy_launches(nullptr, d, j, N, Mz, Ms, fa, fr); });
+    w.on(fb, b_elems, fc, c_elems, [&] {
         sparse_joint_cov_launches(nullptr, d, j, Mz, Ms, fb, fr, fc, nullptr, 0, nullptr, nullptr, 1.0, true);
-    }
-    gaplac_ctx c3;
-    c3.spw = spw;
+    }, fr, r_elems);
     const ExtraRows rows = R > 0 ? ExtraRows::responses(R, nullptr, 0) : ExtraRows{};
-    rc = dry_walk(c3, Ms, rows.on_prebuilt(), g3, short_ws == 3 ? 1 : 0);
-    if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
-    if (out_launches) *out_launches = l0 + g1.launches + g2.launches + g3.launches;
-    if (out_violations) *out_violations = v0 + g1.violations + g2.violations + g3.violations;
-    if (msg && msglen > 0 && v0 == 0) {
-        const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.first;
-        std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
-    }
-    return rc;
+    w.eval(Ms, rows.on_prebuilt(), short_ws == 3 ? 1 : 0);
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of the joint posterior's three stages (no device needed): the posterior
@@ -4608,32 +4463,14 @@ int gaplac_plan_check_joint(int64_t N, int64_t M, int64_t R, int32_t spw, int32_
                             int64_t* out_violations, char* msg, int64_t msglen) {
     if (N < 1 || M < 1 || R < 0 || spw < 1 || spw > 8 || short_ws < 0 || short_ws > 2) return GAPLAC_E_ARG;
     const JointDims d = joint_dims(N, M, R);
-    LaunchGuard g1, g2, g3;
-    gaplac_ctx c1, c3;
-    c1.spw = c3.spw = spw;
-    int rc = dry_walk(c1, N, ExtraRows::test_points(M), g1, short_ws == 1 ? 1 : 0);
-    if (rc == GAPLAC_E_ARG && g1.violations) rc = 0;
-    if (rc == 0) {
-        double* const fa = reinterpret_cast<double*>((uintptr_t)1 << 44);
-        double* const fb = reinterpret_cast<double*>((uintptr_t)1 << 45);
-        g2.base = fa;
-        g2.elems = d.lda * d.Np - (short_ws == 1 ? 1 : 0);
-        g2.base2 = fb;
-        g2.elems2 = d.ldb * d.Mp - (short_ws == 2 ? 1 : 0);
-        g2.dry = true;
-        GuardScope scope(&g2);
-        joint_cov_launches(nullptr, d, N, M, fa, fb, nullptr, nullptr, nullptr, R == 0);
-    }
-    if (rc == 0) {
-        const ExtraRows rows = R > 0 ? ExtraRows::responses(R, nullptr, 0) : ExtraRows{};
-        rc = dry_walk(c3, M, rows.on_prebuilt(), g3, short_ws == 2 ? 1 : 0);
-        if (rc == GAPLAC_E_ARG && g3.violations) rc = 0;
-    }
-    if (out_launches) *out_launches = g1.launches + g2.launches + g3.launches;
-    if (out_violations) *out_violations = g1.violations + g2.violations + g3.violations;
-    const std::string& first = g1.violations ? g1.first : g2.violations ? g2.first : g3.first;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", first.c_str());
-    return rc;
+    double *const fa = PlanWalk::region(0), *const fb = PlanWalk::region(1);
+    PlanWalk w{spw};
+    w.eval(N, ExtraRows::test_points(M), short_ws == 1 ? 1 : 0);
+    w.on(fa, d.lda * d.Np - (short_ws == 1 ? 1 : 0), fb, d.ldb * d.Mp - (short_ws == 2 ? 1 : 0),
+         [&] { joint_cov_launches(nullptr, d, N, M, fa, fb, nullptr, nullptr, nullptr, R == 0); });
+    const ExtraRows rows = R > 0 ? ExtraRows::responses(R, nullptr, 0) : ExtraRows{};
+    w.eval(M, rows.on_prebuilt(), short_ws == 2 ? 1 : 0);
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only walk of one evaluation's schedule (no device needed): every launch's element
@@ -4711,18 +4548,13 @@ int gaplac_plan_check(int64_t N, int32_t mode, int64_t M, int32_t spw, int64_t* 
             return GAPLAC_E_ARG;
         }
     }
-    gaplac_ctx c;
-    c.spw = spw;
     const ExtraRows xr = mode == 1   ? ExtraRows::identity(N)
                          : mode == 2 ? ExtraRows::test_points(M)
                          : mode == 3 ? ExtraRows::responses(M, nullptr, 0)
                                      : ExtraRows{};
-    LaunchGuard g;
-    const int rc = dry_walk(c, N, xr, g, short_ws ? 1 : 0);
-    if (out_launches) *out_launches = g.launches;
-    if (out_violations) *out_violations = g.violations;
-    if (msg && msglen > 0) std::snprintf(msg, (size_t)msglen, "%s", g.first.c_str());
-    return rc == GAPLAC_E_ARG && g.violations ? 0 : rc;
+    PlanWalk w{spw};
+    w.eval(N, xr, short_ws ? 1 : 0);
+    return w.report(out_launches, out_violations, msg, msglen);
 }
 
 // Host-only accounting of the single-GPU schedule: a dry walk of one
@@ -4978,13 +4810,8 @@ int gaplac_laplace_predict(int32_t lik, double lik_param, int64_t M, const doubl
     } else if (Q < 1 || Q > GH_MAX_Q) {
         return GAPLAC_E_ARG;
     }
-    for (int64_t j = 0; ys && j < M; ++j) {
-        const double v = ys[j];
-        const bool ok = lik == GAPLAC_LIK_BERNOULLI ? (v == 0.0 || v == 1.0)
-                        : lik == GAPLAC_LIK_POISSON ? (std::isfinite(v) && v >= 0.0 && v == std::floor(v))
-                                                    : std::isfinite(v);
-        if (!ok) return GAPLAC_E_PARAM;
-    }
+    for (int64_t j = 0; ys && j < M; ++j)
+        if (!lik_supports(lik, ys[j])) return GAPLAC_E_PARAM;
     const bool score = ys && out_logp;
     const GhRule* rule = lik == GAPLAC_LIK_GAUSSIAN ? nullptr : &gh_rule(Q);
     const double sqrt_pi = 1.7724538509055160273, half_log_pi = 0.57236494292470008707;
