@@ -1501,10 +1501,14 @@ int trace_timed(gaplac_ctx* ctx, const char* ext, int64_t a, int64_t b, Stage&& 
 }
 
 // k(x_j, x_j) of row j of a host matrix (the prior variance; a NOISE term counts). With a
-// selector: of component g alone (a term outside it contributes the factor 0.0).
+// selector: of component g alone (a term outside it contributes the factor 0.0). noise_groups:
+// the product groups that hold a NOISE term alone (0 across point sets: the diagonal part of K
+// that a matrix-free product leaves out).
+constexpr bool NOISE_GROUPS_ONLY = true;  // host_kdiag's last argument
 double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j, const CompSel* sel = nullptr,
-                  int32_t g = 0) {
+                  int32_t g = 0, bool noise_groups = false) {
     double kd = 0.0, pr = 1.0;
+    bool has_noise = false;
     for (int t = 0; t < tp.T; ++t) {
         const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + j];
         double k = 1.0;  // CAT: kappa(d) = d > 0 ? 0 : 1 is 1 at any x, NaN included
@@ -1512,11 +1516,15 @@ double host_kdiag(const TermPack& tp, const double* X, int64_t ldx, int64_t j, c
         // (u - u is NaN: the Gram's diagonal there)
         if ((tp.kind[t] == GAPLAC_SQEXP || tp.kind[t] == GAPLAC_OU) && !std::isfinite(tp.p[t] * x)) k = NAN;
         if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
-        if (tp.kind[t] == GAPLAC_NOISE) k = tp.p[t];
+        if (tp.kind[t] == GAPLAC_NOISE) {
+            k = tp.p[t];
+            has_noise = true;
+        }
         pr *= !sel || sel->comp[t] == g ? k : 0.0;
         if (tp.last_in_group[t]) {
-            kd += pr;
+            if (has_noise || !noise_groups) kd += pr;
             pr = 1.0;
+            has_noise = false;
         }
     }
     return kd;
@@ -3123,30 +3131,6 @@ static void lap_grad_bilinear_launches(hipStream_t s, const LapDims& d, int64_t 
     launch_laplace_grad_bilinear(s, N, T, X, N, lap + d.ug, lap + d.a, dtp, dgp, lap + d.gpart, lap + d.gimp);
 }
 
-// The diagonal part of K at training point i that the matrix-free product leaves out: every
-// product group with a NOISE term (0 across point sets), at x_i against itself.
-static double host_noise_diag(const TermPack& tp, const double* X, int64_t ldx, int64_t i) {
-    double kd = 0.0, pr = 1.0;
-    bool has = false;
-    for (int t = 0; t < tp.T; ++t) {
-        const double x = tp.kind[t] == GAPLAC_NOISE ? 0.0 : X[(int64_t)tp.col[t] * ldx + i];
-        double k = 1.0;
-        if ((tp.kind[t] == GAPLAC_SQEXP || tp.kind[t] == GAPLAC_OU) && !std::isfinite(tp.p[t] * x)) k = NAN;
-        if (tp.kind[t] == GAPLAC_LINEAR) k = x * x + tp.p[t];
-        if (tp.kind[t] == GAPLAC_NOISE) {
-            k = tp.p[t];
-            has = true;
-        }
-        pr *= k;
-        if (tp.last_in_group[t]) {
-            if (has) kd += pr;
-            pr = 1.0;
-            has = false;
-        }
-    }
-    return kd;
-}
-
 template <typename Launches>
 static int lap_on_ws(gaplac_ctx* ctx, Launches&& launches) {
     return guarded_on(ctx, ctx->A, ctx->A_elems, ctx->lap, ctx->lap_elems, launches, ctx->dY, ctx->dY_elems);
@@ -3364,7 +3348,7 @@ static int lap_upload(gaplac_ctx* ctx, const LapRequest& q, const LapDims& d, co
     }
     {
         std::vector<double> diag((size_t)N);
-        for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = q.jitter + host_noise_diag(tp, q.X, q.ldx, i);
+        for (int64_t i = 0; i < N; ++i) diag[(size_t)i] = q.jitter + host_kdiag(tp, q.X, q.ldx, i, nullptr, 0, NOISE_GROUPS_ONLY);
         HIPCK(ctx, hipMemcpyAsync(lap + d.diag, diag.data(), (size_t)N * 8, hipMemcpyHostToDevice, s));
         HIPCK(ctx, hipStreamSynchronize(s));  // (diag is the host's: it ends with this block)
     }

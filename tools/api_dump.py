@@ -1,4 +1,4 @@
-"""Every output of the Laplace, joint, sparse-joint and fit entries at the smallest shapes that cross
+"""Every output of the Laplace, joint, sparse-joint, fit and row-kernel entries at the smallest shapes that cross
 a tile edge and a chunk edge, as .npy files, and their sha256.
 
     python tools/api_dump.py --out DIR            (GAPLAC_LIB_PATH picks another build)
@@ -7,6 +7,7 @@ The behaviour check of a host-only change: summation orders are functions of the
 builds (and two runs of one) must hash identically. One error case per entry goes into errors.npy. Needs a GPU.
 """
 import hashlib
+import itertools
 import os
 import sys
 import warnings
@@ -19,13 +20,44 @@ from gaplac_amd.backend import ArgumentError, Context, GaplacError, PosDefExcept
 
 SINGLE = [(_native.SQEXP, 0, 1.5, 0), (_native.OU, 0, 3.0, 1), (_native.CAT, 1, 0.0, 2)]
 PRODUCT = [(_native.SQEXP, 0, 1.5, 0), (_native.CAT, 1, 0.0, 0), (_native.OU, 0, 3.0, 1)]
+MIXED = [(_native.SQEXP, 0, 1.5, 0), (_native.LINEAR, 0, 0.5, 0), (_native.OU, 0, 3.0, 1), (_native.NOISE, 0, 0.2, 1),
+         (_native.CAT, 1, 0.0, 2)]  # every branch of term_k: a LINEAR and a NOISE term inside product groups
+TERM_SETS = (("single", SINGLE, (0, 1, 2)), ("product", PRODUCT, (0, 0, 2)), ("mixed", MIXED, (0, 0, 1, 1, 2)))
 NS, LAP_MS, MS, RS, MZS = (129, 300), (0, 3, 129, 4097), (3, 129), (1, 129), (5, 130)  # 4097 crosses LAP_CHUNK
 JITTER, NOISE, NOISE_S, CAP = 1e-6, 0.1, 0.05, 1024
+ROW_NS, ROW_MS, ROW_MZS = NS + (513,), MS + (513,), MZS + (513,)  # 513: more than one 512-column chunk
 
 
 def inputs(n, seed):
     rng = np.random.default_rng(seed)
     return np.column_stack([rng.uniform(0, 10, n), rng.integers(0, 7, n).astype(float)]).reshape(n, 2)
+
+
+def row_entries(ctx, rng, save):
+    """The entries that sum over riding rows: posterior, components, gradient, draws, matrix forms, an exact
+    fit's queries and the sparse bound, per term set. A refused call raises: every entry is in the hashes."""
+    for N, (tname, terms, comp) in itertools.product(ROW_NS, TERM_SETS):
+        X, y, z = inputs(N, N), rng.standard_normal(N), rng.standard_normal(N)
+        tag, ex = f"rows_N{N}_{tname}", (X, terms, NOISE, y)
+        save(tag + "_logpdf_grad", *ctx.logpdf_grad(*ex))
+        save(tag + "_rand", ctx.rand(X, terms, NOISE, z))
+        for R in RS:
+            multi = (X, terms, NOISE, rng.standard_normal((N, R)))
+            save(f"{tag}_R{R}_multi", *ctx.logpdf_multi(*multi, full=True), ctx.rand_multi(*multi))
+        with ctx.fit(*ex, cap=CAP) as fit:
+            save(tag + "_fit_alpha", fit.alpha())
+            for M in ROW_MS:
+                Xs = inputs(M, 2000 + M)
+                save(f"{tag}_M{M}_fit", fit.mean(Xs), *fit.mean_var(Xs))
+                save(f"{tag}_M{M}_mean_var", *ctx.posterior_mean_var(*ex, Xs))
+                save(f"{tag}_M{M}_comp", *ctx.posterior_components(*ex, Xs, [0] * len(terms)),
+                     *ctx.posterior_components(*ex, Xs, comp, G=3))
+        for Mz in ROW_MZS:
+            sp = (*ex, inputs(Mz, 3000 + Mz), JITTER)
+            save(f"{tag}_Mz{Mz}_elbo", *ctx.sparse_elbo(*sp, full=True).values())
+            save(f"{tag}_Mz{Mz}_elbo_grad", *ctx.sparse_elbo_grad(*sp), *ctx.sparse_elbo_grad(*sp, wrt_z=True))
+            for M in ROW_MS:
+                save(f"{tag}_Mz{Mz}_M{M}_mean_var", *ctx.sparse_posterior_mean_var(*sp, inputs(M, 2000 + M)))
 
 
 def main():
@@ -55,7 +87,7 @@ def main():
                 tag = f"lap_N{N}_{lik}"
                 r = ctx.laplace_logpdf(*lap, full=True)
                 save(tag + "_logpdf", r.logq, r.f, r.a, r.iters, r.converged)
-                for tname, terms in (("single", SINGLE), ("product", PRODUCT)):
+                for tname, terms, _ in TERM_SETS:
                     g = ctx.laplace_logpdf_grad(X, terms, JITTER, lik, yl)
                     save(f"{tag}_grad_{tname}", g.logq, g.f, g.a, g.dparam, g.djitter, g.implicit, g.iters)
                 with ctx.laplace_fit(*lap, cap=CAP) as fit:
@@ -83,6 +115,7 @@ def main():
                             keep(f"exact_{tag}_logpdf", *ctx.posterior_logpdf(*ex, NOISE_S, Ys, full=True))
                         save(f"sparse_Mz{Mz}_{tag}_rand", ctx.sparse_posterior_rand(*sp, NOISE_S, E))
                         keep(f"sparse_Mz{Mz}_{tag}_logpdf", *ctx.sparse_posterior_logpdf(*sp, NOISE_S, Ys, full=True))
+        row_entries(ctx, rng, save)
         # one refused call per entry
         X, y, Xs, Z = inputs(5, 1), np.ones(5), inputs(3, 2), inputs(2, 3)
         E = np.zeros((3, 2))
